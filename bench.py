@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Gibbs hot path on MI355X, one independent chain per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--model lsm|hdp|all]
+    python bench.py --gpus N --steps K --warmup W [--model lsm|hdp|all] [--dump-outputs DIR]
 
 Headline (``--model lsm``, BASELINE.json configs[1]): Gibbs iterations/s of
 DynamicNetworkLSM on a synthetic undirected network, T=10 N=2000 d=2.  One "step" =
@@ -67,6 +67,9 @@ F64_VALU_SUSTAINED_FRAC = 0.82
 OPS_PER_TERM_SWEEP = 34
 OPS_PER_TERM_LOGLIK = 17
 
+
+# --dump-outputs: bytes written at most; above it every large array is a fixed, seeded sample
+DUMP_BUDGET_BYTES = 64 << 20
 
 _INSTR_CACHE = []
 
@@ -141,6 +144,10 @@ def parse(argv=None):
     ap.add_argument('--force-collectives', action='store_true',
                     help='with --gpus 1: initialise the backend anyway and route the broadcast / '
                          'gather / barrier through it (exercises RCCL on a single-GPU box)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what each timed workload computed in its last timed '
+                         'step (rank 0\'s chains) as DIR/<model>_<array>.npy, float64, %d MB at most in all'
+                         % (DUMP_BUDGET_BYTES >> 20))
     ap.add_argument('--share-device0', action='store_true',
                     help='dry run: every rank drives cuda:0 (with --backend gloo)')
     return ap.parse_args(argv)
@@ -275,6 +282,13 @@ class LsmWorkload(object):
             Xs, ics, lps = ch.trace_read(first, count, positions=True)
             out.append(dict(X_mean=Xs.mean(axis=0), logps=lps, intercepts=ics))
         return {k: np.stack([o[k] for o in out]) for k in out[0]}
+
+    def outputs(self, it):
+        """what dlsm_lsm_run stored for iteration `it`, per chain of this rank"""
+        rows = [ch.trace_read(it, 1, positions=True) for ch in self.chains]
+        return {'positions': np.stack([r[0][0] for r in rows]),
+                'intercepts': np.stack([r[1][0] for r in rows]),
+                'logp': np.array([r[2][0] for r in rows])}
 
     def acceptance(self):
         from dynetlsm_amd import SamplerGrid
@@ -644,6 +658,14 @@ class HdpWorkload(object):
                             n_clusters_used=(nk > 0).any(axis=1).sum(axis=1).astype(np.float64)))
         return {k: np.stack([o[k] for o in out]) for k in out[0]}
 
+    def outputs(self, it):
+        """the stored sample of iteration `it`, per chain of this rank (labels as float64)"""
+        rows = [m.chain_.hdp_trace_read(it, 1) for m in self.models]
+        names = {'Xs': 'positions', 'zs': 'labels', 'intercepts': 'intercepts', 'logps': 'logp',
+                 'mus': 'mus', 'sigmas': 'sigmas', 'betas': 'betas', 'weights': 'weights',
+                 'lambdas': 'lambdas', 'hypers': 'hypers'}
+        return {v: np.stack([r[k][0] for r in rows]).astype(np.float64) for k, v in names.items()}
+
     def acceptance(self):
         m = self.model
         g = m.chain_.get_samplers(m.latent_samplers)
@@ -937,6 +959,14 @@ class CcWorkload(object):
         g = self.chain.get_samplers(SamplerGrid(self.T, self.N, self.step_x, tune=None))
         return float(g.n_accepted.sum()) / max(float(g.n_steps.sum()), 1.0)
 
+    def outputs(self, it):
+        """what dlsm_lsm_run stored for iteration `it`, per chain of this rank"""
+        rows = [ch.trace_read(it, 1, positions=True) for ch in self.chains]
+        return {'positions': np.stack([r[0][0] for r in rows]),
+                'intercepts': np.stack([r[1][0] for r in rows]),
+                'logp': np.array([r[2][0] for r in rows]),
+                'radii': np.stack([ch.trace_read_radii(it, 1)[0] for ch in self.chains])}
+
     def cpu_baseline(self):
         """rank 0: the oracle's restatement of the same iteration (scalar C sweep and case-control
         log-likelihoods; the radii's Dirichlet proposal in numpy) with the chain's controls"""
@@ -1024,6 +1054,7 @@ def measure(wl, args, group):
     group.barrier()
     mine = time.perf_counter() - t0
     elapsed = group.max_over_ranks(mine)
+    wl.last_timed_iteration = wl.next_it - 1        # (--dump-outputs: the trace row of the last timed step)
     tb = time.perf_counter()
     group.barrier()                 # what the closing barrier of the timed region costs by itself
     wl.barrier_ms = 1e3 * (time.perf_counter() - tb)
@@ -1056,6 +1087,22 @@ def chain_summaries(g):
     return out
 
 
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """arrays as out_dir/<name>.npy in float64.  Above `budget` bytes in all, every array larger than
+    its even share is replaced by the same seeded sample of its flattened entries, written beside
+    it as <name>_sample_index.npy (the flat indices, ascending)"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    share = budget // max(2 * len(arrays), 1) // 8          # entries per array (value + index)
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in sorted(arrays.items()):
+        if total > budget and v.size > share:
+            idx = np.sort(np.random.RandomState(0).choice(v.size, share, replace=False))
+            np.save(os.path.join(out_dir, name + '_sample_index.npy'), idx.astype(np.float64))
+            v = v.ravel()[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), v)
+
+
 def run_rank(args):
     import torch
     rank = int(os.environ.get('RANK', '0'))
@@ -1082,6 +1129,7 @@ def run_rank(args):
         kernel_instr_per_term()         # host-only, cached: not between the profile phase and the timed steps
     models = ['lsm', 'hdp', 'cc', 'ccu'] if args.model == 'all' else [args.model]
     lines = []
+    dumped = {}
     def run_model(name, args=args):
             K, W = args.steps, args.warmup          # (the extra configurations pass their own window)
             wl = {'lsm': LsmWorkload, 'hdp': HdpWorkload, 'cc': CcWorkload,
@@ -1151,6 +1199,8 @@ def run_rank(args):
                     line['n_clusters_used_last'] = [float(v[-1]) for v in gathered['n_clusters_used']]
                 line.update(extra)
                 lines.append(line)
+            if rank == 0 and args.dump_outputs:
+                dumped.update({'%s_%s' % (name, k): v for k, v in wl.outputs(wl.last_timed_iteration).items()})
             wl.close()
 
     def run_monks():
@@ -1261,6 +1311,8 @@ def run_rank(args):
                 'also_c4_degree_regular_network_it_per_s': val(lambda ln: 'degree-regular' in ln['metric']),
                 'also_c1_monks_it_per_s': val(lambda ln: 'monks' in ln['metric']),
                 'also_c2_4_chains_per_gpu_aggregate_it_per_s': val(lambda ln: ln.get('chains_per_gpu') == 4)})
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(head), flush=True)
     group.close()
 
