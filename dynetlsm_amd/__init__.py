@@ -12,8 +12,9 @@ from .hdp_lpcm import DynamicNetworkHDPLPCM  # noqa
 from .lpcm import DynamicNetworkLPCM  # noqa
 from .case_control import DirectedCaseControlSampler  # noqa
 from . import metrics  # noqa
+from .gof import posterior_predictive_check, GofResult  # noqa
 
 __version__ = '0.1.0'
 __all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
            'DynamicNetworkLSM', 'DynamicNetworkHDPLPCM', 'DynamicNetworkLPCM',
-           'DirectedCaseControlSampler']
+           'DirectedCaseControlSampler', 'posterior_predictive_check', 'GofResult']

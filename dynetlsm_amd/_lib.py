@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('DLSM_LIB') or os.path.join(HERE, 'libdynetlsm_hip.so'
 c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
 c_i32_p = C.POINTER(C.c_int32)
+c_u32_p = C.POINTER(C.c_uint32)
 handle_t = C.c_void_p
 
 (K_LOGLIK, K_SWEEP, K_CENTER, K_LABELS, K_FINALIZE, K_SWEEP_EVAL, K_SWEEP_RESOLVE,
@@ -155,6 +156,9 @@ SIGNATURES = {
                                             c_double_p]),
     'dlsm_forecast_marginal': (C.c_int, [handle_t, c_double_p, c_double_p, c_double_p, C.c_int,
                                          c_double_p]),
+    'dlsm_gof_simulate': (C.c_int, [handle_t, c_double_p, c_double_p, c_double_p, C.c_int, C.c_uint64,
+                                    C.c_uint32, C.c_int, c_i64_p, c_u32_p]),
+    'dlsm_gof_observed': (C.c_int, [handle_t, c_u32_p, c_i64_p]),
     'dlsm_host_sample_tables': (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p,
                                           C.c_double, C.c_double, C.c_double, c_i64_p]),
     'dlsm_profile_enable': (C.c_int, [handle_t, C.c_int]),

@@ -29,6 +29,7 @@
 #include "kernels_init.hpp"
 #include "kernels_post.hpp"
 #include "kernels_forecast.hpp"
+#include "kernels_gof.hpp"
 #include "host_draws.hpp"
 
 using namespace dlsm;
@@ -2181,6 +2182,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_init.hpp"
 #include "capi_post.hpp"
 #include "capi_forecast.hpp"
+#include "capi_gof.hpp"
 #include "capi_hdp.hpp"
 
 extern "C" int dlsm_host_sample_tables(void *numpy_bitgen, int T, int K, const double *n,

@@ -1,0 +1,121 @@
+// C-ABI of the posterior predictive goodness-of-fit check (kernels_gof.hpp; included by capi.hip after
+// capi_forecast.hpp).  The reference has no counterpart.
+#pragma once
+
+namespace {
+
+constexpr size_t GOF_SCRATCH_BYTES = (size_t)256 << 20;   // device scratch of one batch (auto batching)
+
+int gof_lanes_per_row(int W) {
+    int L = 1;
+    while (L < W / 4 && L < 64) L <<= 1;
+    return L;
+}
+
+// statistics of `nets` networks: rows (and trows, directed) [nets][N][W] on the device -> dstats
+// [nets][R], zeroed here
+int gof_stats_launch(dlsm_chain *h, const uint32_t *rows, const uint32_t *trows, int nets, int64_t *dstats) {
+    const int N = h->N, W = h->W;
+    const size_t R = 2 + 3 * (size_t)N;
+    HIPCHK(h, hipMemsetAsync(dstats, 0, (size_t)nets * R * sizeof(int64_t), h->stream));
+    const int nbx = std::max(1, std::min(N, 8192 / nets));
+    hipLaunchKernelGGL(k_gof_stats, dim3(nbx, nets), dim3(256), 0, h->stream, rows, trows, N, W,
+                       gof_lanes_per_row(W), dstats);
+    HIPCHK(h, hipGetLastError());
+    return DLSM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dlsm_gof_simulate(dlsm_chain *h, const double *Xs, const double *intercepts, const double *radii, int S,
+                      uint64_t seed, uint32_t first_index, int batch, int64_t *stats, uint32_t *bits) {
+    NEED(h, h && Xs && intercepts && stats, "null argument");
+    const bool directed = h->model != DLSM_UNDIRECTED;
+    NEED(h, !directed || radii, "directed models need the radii");
+    NEED(h, S >= 1, "needs at least one sample");
+    NEED(h, batch >= 0, "batch must be >= 0 (0: automatic)");
+    NEED(h, (uint64_t)first_index + (uint64_t)S <= ((uint64_t)1 << 32), "first_index + S must be <= 2^32");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int T = h->T, N = h->N, D = h->D, W = h->W;
+    const size_t R = 2 + 3 * (size_t)N, net_words = (size_t)N * W, nmat = directed ? 2 : 1;
+    const size_t per_sample = (size_t)T * (net_words * nmat * sizeof(uint32_t) + R * sizeof(int64_t) +
+                                           (size_t)N * D * sizeof(double));
+    int nb = batch > 0 ? batch : (int)std::max<size_t>(1, GOF_SCRATCH_BYTES / per_sample);
+    nb = std::min(nb, S);
+    nb = std::min(nb, std::max(1, 65535 / T));          // networks of a batch: the grid's y extent
+    DevBuf bX, bB, bR, bBits, bS;
+    HIPCHK(h, hipMalloc(&bX.p, (size_t)nb * T * N * D * sizeof(double)));
+    HIPCHK(h, hipMalloc(&bB.p, (size_t)nb * 2 * sizeof(double)));
+    if (directed) HIPCHK(h, hipMalloc(&bR.p, (size_t)nb * N * sizeof(double)));
+    HIPCHK(h, hipMalloc(&bBits.p, (size_t)nb * T * net_words * nmat * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&bS.p, (size_t)nb * T * R * sizeof(int64_t)));
+    const unsigned gx = (unsigned)((net_words + 255) / 256);
+    for (int s0 = 0; s0 < S; s0 += nb) {
+        const int n = std::min(nb, S - s0), nets = n * T;
+        HIPCHK(h, hipMemcpyAsync(bX.p, Xs + (size_t)s0 * T * N * D, (size_t)nets * N * D * sizeof(double),
+                                 hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(bB.p, intercepts + 2 * (size_t)s0, (size_t)n * 2 * sizeof(double),
+                                 hipMemcpyHostToDevice, h->stream));
+        if (directed)
+            HIPCHK(h, hipMemcpyAsync(bR.p, radii + (size_t)s0 * N, (size_t)n * N * sizeof(double),
+                                     hipMemcpyHostToDevice, h->stream));
+        DISPATCH_D(h, D, hipLaunchKernelGGL((k_gof_draw<DD>), dim3(gx, nets, (unsigned)nmat), dim3(256), 0,
+                                            h->stream, bX.as<double>(), bB.as<double>(),
+                                            directed ? bR.as<double>() : nullptr, T, N, W, (int)directed,
+                                            seed, first_index + (uint32_t)s0, bBits.as<uint32_t>()));
+        HIPCHK(h, hipGetLastError());
+        const uint32_t *rows = bBits.as<uint32_t>();
+        int rc = gof_stats_launch(h, rows, directed ? rows + (size_t)nets * net_words : nullptr, nets,
+                                  bS.as<int64_t>());
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(stats + (size_t)s0 * T * R, bS.p, (size_t)nets * R * sizeof(int64_t),
+                                 hipMemcpyDeviceToHost, h->stream));
+        if (bits)
+            HIPCHK(h, hipMemcpyAsync(bits + (size_t)s0 * T * net_words, rows,
+                                     (size_t)nets * net_words * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                     h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return DLSM_OK;
+}
+
+int dlsm_gof_observed(dlsm_chain *h, const uint32_t *bits, int64_t *stats) {
+    NEED(h, h && bits && stats, "null argument");
+    const int T = h->T, N = h->N, W = h->W;
+    const size_t R = 2 + 3 * (size_t)N, net_words = (size_t)N * W;
+    // the padding bits and the diagonal are zero
+    for (size_t row = 0; row < (size_t)T * N; ++row) {
+        const uint32_t *r = bits + row * W;
+        const int i = (int)(row % N);
+        if ((r[i >> 5] >> (i & 31)) & 1u)
+            FAIL(h, DLSM_E_DATA, "network has a self-loop (t=%d, i=%d)", (int)(row / N), i);
+        for (int w = N >> 5; w < W; ++w) {
+            const int lo = 32 * w;
+            const uint32_t pad = lo >= N ? 0xFFFFFFFFu : ~((1u << (N - lo)) - 1u);
+            if (r[w] & pad) FAIL(h, DLSM_E_DATA, "padding bits beyond column N-1 must be zero");
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const bool directed = h->model != DLSM_UNDIRECTED;
+    DevBuf bBits, bT, bS;
+    HIPCHK(h, hipMalloc(&bBits.p, (size_t)T * net_words * sizeof(uint32_t)));
+    if (directed) HIPCHK(h, hipMalloc(&bT.p, (size_t)T * net_words * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&bS.p, (size_t)T * R * sizeof(int64_t)));
+    HIPCHK(h, hipMemcpyAsync(bBits.p, bits, (size_t)T * net_words * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             h->stream));
+    if (directed) {
+        hipLaunchKernelGGL(k_gof_transpose, dim3((unsigned)((net_words + 255) / 256), T), dim3(256), 0,
+                           h->stream, bBits.as<uint32_t>(), N, W, bT.as<uint32_t>());
+        HIPCHK(h, hipGetLastError());
+    }
+    int rc = gof_stats_launch(h, bBits.as<uint32_t>(), directed ? bT.as<uint32_t>() : nullptr, T,
+                              bS.as<int64_t>());
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(stats, bS.p, (size_t)T * R * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DLSM_OK;
+}
+
+}  // extern "C"

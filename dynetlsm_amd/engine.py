@@ -28,6 +28,23 @@ def check_n_features(n_features):
     return d
 
 
+def packed_row_words(N):
+    """uint32 words of one bit-packed network row (capi.hip dlsm_create: a multiple of 4)"""
+    return ((int(N) + 31) // 32 + 3) // 4 * 4
+
+
+def pack_network(Y):
+    """(T, N, N) 0/1 array -> (T, N, W) uint32 rows in the engine's layout: bit j % 32 of word
+    j // 32 of row i is Y[t, i, j]; padding bits are zero"""
+    Y = np.asarray(Y)
+    T, N = Y.shape[0], Y.shape[1]
+    W = packed_row_words(N)
+    B = np.zeros((T, N, 32 * W), dtype=np.uint8)
+    B[:, :, :N] = Y != 0
+    bytes_ = np.packbits(B, axis=-1, bitorder='little')
+    return np.ascontiguousarray(bytes_).view('<u4').astype(np.uint32).reshape(T, N, W)
+
+
 def _f64(a, shape=None, name='array'):
     a = np.ascontiguousarray(a, dtype=np.float64)
     if shape is not None and tuple(a.shape) != tuple(shape):
@@ -671,6 +688,49 @@ class Chain(object):
         out = np.empty((self.N, self.N))
         self._ck(self._L.dlsm_forecast_marginal(self._h, _p(x), _p(W), _p(b), S, _p(out)))
         return out
+
+    # -- posterior predictive goodness of fit (no reference counterpart) ----------------------
+    def gof_record_length(self):
+        """int64 entries of one statistics record: edges, mutual, deg_out[N], deg_in[N], esp[N]"""
+        return 2 + 3 * self.N
+
+    def gof_simulate(self, Xs, intercepts, radii=None, seed=0, first_index=0, batch=0, want_bits=False):
+        """Networks drawn at the S posterior samples ``Xs`` (S, T, N, D), ``intercepts`` (S,) or (S, 2),
+        ``radii`` (S, N) (directed and case-control chains), and their statistics (S, T, R) int64.
+        Sample s uses RNG index ``first_index + s``: results do not depend on how the samples are split
+        across calls or on ``batch`` (samples per device batch, 0: automatic).  ``want_bits``: also the
+        drawn rows (S, T, N, W) uint32, bit j % 32 of word j // 32 of row i = Y[t, i, j]."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        S = Xs.shape[0]
+        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
+        b = np.asarray(intercepts, dtype=np.float64)
+        if b.ndim == 1 and self.model == UNDIRECTED:
+            b = np.stack([b, np.zeros_like(b)], axis=1)
+        b = _f64(b, (S, 2), 'intercepts')
+        if self.model == UNDIRECTED:
+            r = None
+        else:
+            if radii is None:
+                raise ValueError('directed models need radii')
+            r = _f64(radii, (S, self.N), 'radii')
+        stats = np.zeros((S, self.T, self.gof_record_length()), dtype=np.int64)
+        W = packed_row_words(self.N)
+        bits = np.zeros((S, self.T, self.N, W), dtype=np.uint32) if want_bits else None
+        self._ck(self._L.dlsm_gof_simulate(
+            self._h, _p(Xs), _p(b), _p(r) if r is not None else None, int(S),
+            C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(first_index)), int(batch), _p(stats),
+            bits.ctypes.data_as(_lib.c_u32_p) if want_bits else None))
+        return (stats, bits) if want_bits else stats
+
+    def gof_observed(self, bits):
+        """statistics (T, R) int64 of the packed network ``bits`` (T, N, W) uint32 (``pack_network``)"""
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        if bits.shape != (self.T, self.N, packed_row_words(self.N)):
+            raise ValueError('bits has shape %s, expected %s'
+                             % (bits.shape, (self.T, self.N, packed_row_words(self.N))))
+        stats = np.zeros((self.T, self.gof_record_length()), dtype=np.int64)
+        self._ck(self._L.dlsm_gof_observed(self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(stats)))
+        return stats
 
     def profile_enable(self, on=True):
         self._ck(self._L.dlsm_profile_enable(self._h, int(on)))

@@ -379,6 +379,30 @@ int dlsm_forecast_mean_probas(dlsm_chain *h, const double *Xs, const double *int
 int dlsm_forecast_marginal(dlsm_chain *h, const double *x, const double *W, const double *intercepts,
                            int S, double *out);
 
+/* ---- posterior predictive goodness of fit ------------------------------ */
+/* No reference counterpart (the check of latentnet's / ergm's gof()).  A record of R = 2 + 3N int64
+ * per (sample, t): [0] edges (num_edges of network_statistics.py:13-14: undirected pairs, or
+ * directed arcs), [1] mutual (pairs i < j with both arcs; 0 undirected), [2 + k] nodes of out-degree
+ * k (undirected: the degree), [2 + N + k] nodes of in-degree k (0 undirected), [2 + 2N + k] edges
+ * with k shared partners (undirected: pairs i < j with an edge, common neighbours; directed: arcs
+ * i -> j, nodes m with i -> m -> j), k = 0..N-1.  Packed networks are [T][N][W] uint32, bit j % 32 of
+ * word j / 32 of row i = Y[t, i, j], W = dlsm_network_packed_words / (T N) of an undirected handle
+ * of the same N (a multiple of 4), padding bits zero. */
+/* posterior predictive draws and their statistics: Xs S*T*N*D, intercepts S*2 (undirected models
+ * read [s][0]; directed [s] = (intercept_in, intercept_out)), radii S*N (directed and case-control
+ * handles; NULL otherwise); sample s uses RNG index first_index + s (Philox4x32-10 keyed by `seed`,
+ * counter (min(i,j), max(i,j), index, t<<8|7): results do not depend on how the samples are split
+ * across calls or batches); batch = samples per device batch (0: automatic, bounded scratch);
+ * stats S*T*R int64; bits NULL or S*T*N*W uint32 (the drawn networks' rows).  Directed draws
+ * (the exact model of metrics.py:57-60) for directed and case-control handles. */
+int dlsm_gof_simulate(dlsm_chain *h, const double *Xs, const double *intercepts, const double *radii,
+                      int S, uint64_t seed, uint32_t first_index, int batch, int64_t *stats,
+                      uint32_t *bits);
+/* the same statistics (no reference counterpart; edges as network_statistics.py:13-14) of a packed
+ * network `bits` T*N*W uint32 supplied by the caller; stats T*R int64.  A set diagonal or padding
+ * bit -> DLSM_E_DATA. */
+int dlsm_gof_observed(dlsm_chain *h, const uint32_t *bits, int64_t *stats);
+
 /* ---- host-stream auxiliary draws ----------------------- */
 /* sample_tables (sample_auxillary.py:6-28): m T*K*K int64 = tables per (restaurant, dish)
  * given the transition counts n T*K*K (n[0,0,:] = initial counts) and beta K.  The
