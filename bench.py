@@ -1,7 +1,16 @@
 #!/usr/bin/env python
 """Benchmark of the Gibbs hot path on MI355X, one independent chain per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--model lsm|hdp|all] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--full] [--model lsm|hdp|all] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: it sets up the headline workload, runs its
+untimed settle and W warm-up steps, times the K steps and prints the line.  ``--dump-outputs`` without
+``--model`` writes the outputs of every workload of ``--model all`` (LSM, HDP-LPCM and both case-control
+networks), so a plain run with it sets up and times those three as well, as ``extra_configs``, without
+their profile or CPU baseline.  ``--full`` adds everything else the benchmark measures or checks: the
+other configurations (``--model all``), the per-kernel profile behind the timed window with its rooflines
+(``--profile-steps``) and the CPU baselines with the engine's agreement with the oracle (``--cpu-iters``).
+An option given explicitly holds either way.
 
 Headline (``--model lsm``, BASELINE.json configs[1]): Gibbs iterations/s of
 DynamicNetworkLSM on a synthetic undirected network, T=10 N=2000 d=2.  One "step" =
@@ -19,9 +28,9 @@ HDP's auxiliary / conjugate / hyper-parameter draws and the log-posterior trace.
 DynamicNetworkLSM (T=5 N=10 000, 100 controls): sweep over the case-control partial
 likelihoods, centring, the two intercept steps and the radii step.
 
-``--model all`` (the default) prints the LSM line as the headline - the metric of
+``--model all`` (the default of ``--full``) prints the LSM line as the headline - the metric of
 BASELINE.json - and attaches the HDP-LPCM and case-control measurements of the same run as
-``extra_configs`` (so that the N-GPU runs exercise configs[4] too).  ``--chains-per-gpu C``
+``extra_configs`` (so that the N-GPU runs with ``--full`` exercise configs[4] too).  ``--chains-per-gpu C``
 runs C independent chains per GPU, each on its own handle, stream and host thread.
 
 N > 1: when RANK is not set the process spawns the N ranks itself (it makes no GPU
@@ -105,10 +114,16 @@ def parse(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--model', default='all', choices=['lsm', 'hdp', 'cc', 'ccu', 'all'],
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: every configuration '
+                         '(--model all), the per-kernel profile and rooflines (--profile-steps 100) and the '
+                         'CPU baselines with their checks against the oracle (--cpu-iters 8); an option given '
+                         'explicitly overrides what --full implies')
+    ap.add_argument('--model', default=None, choices=['lsm', 'hdp', 'cc', 'ccu', 'all'],
                     help="cc: config 4 on a network drawn FROM the model (the quoted figure); ccu: on the "
                          "degree-regular network of rounds 1-5 (every node draws 20 out-neighbours uniformly: "
-                         "the labelled easy case); all: lsm, hdp, cc, ccu, monks and lsm at 4 chains per GPU")
+                         "the labelled easy case); all: lsm, hdp, cc, ccu, monks and lsm at 4 chains per GPU.  "
+                         "Default: lsm, all with --full")
     ap.add_argument('--T', type=int, default=10)
     ap.add_argument('--N', type=int, default=2000)
     ap.add_argument('--D', type=int, default=2)
@@ -121,9 +136,10 @@ def parse(argv=None):
                     help='independent chains per GPU, each on its own handle and stream, '
                          'enqueued by its own host thread (aggregate throughput)')
     ap.add_argument('--algo', type=int, default=0, help='sweep algorithm (0 auto)')
-    ap.add_argument('--profile-steps', type=int, default=100,
+    ap.add_argument('--profile-steps', type=int, default=None,
                     help='iterations of the per-kernel event phase (averages over 100 x 18 sweep launches); it runs '
-                         'BEHIND the timed window since round 5: a 20-step window behind it read 2-6 %% low')
+                         'BEHIND the timed window since round 5: a 20-step window behind it read 2-6 %% low.  '
+                         'Default: 0, 100 with --full')
     ap.add_argument('--settle-steps', type=int, default=300,
                     help='plain untimed iterations of every chain in front of the W warm-up steps (reported in the '
                          'line as untimed_steps_before_warmup): the chain starts on a device that sat idle through '
@@ -134,8 +150,8 @@ def parse(argv=None):
     ap.add_argument('--windows', type=int, default=1,
                     help='diagnostic: time this many further windows of K steps behind the contract\'s one '
                          '(reported as later_windows; `value` is always the first window)')
-    ap.add_argument('--cpu-iters', type=int, default=8,
-                    help='oracle iterations timed for cpu_baseline (0 = skip)')
+    ap.add_argument('--cpu-iters', type=int, default=None,
+                    help='oracle iterations timed for cpu_baseline (0 = skip).  Default: 0, 8 with --full')
     ap.add_argument('--cpu-procs', type=int, default=1,
                     help='also time this many independent CPU chains in as many processes')
     ap.add_argument('--no-cpu', action='store_true')
@@ -150,7 +166,16 @@ def parse(argv=None):
                          % (DUMP_BUDGET_BYTES >> 20))
     ap.add_argument('--share-device0', action='store_true',
                     help='dry run: every rank drives cuda:0 (with --backend gloo)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    # --dump-outputs without --model writes what every workload of --model all computes, with --full or
+    # without: a plain run then times the other three workloads too (without their profile or CPU baseline)
+    dump_all = args.model is None and args.dump_outputs is not None
+    # what --full implies, for the options not given explicitly
+    for name, plain, full in (('model', 'lsm', 'all'), ('profile_steps', 0, 100), ('cpu_iters', 0, 8)):
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else plain)
+    args.workloads = ['lsm', 'hdp', 'cc', 'ccu'] if args.model == 'all' or dump_all else [args.model]
+    return args
 
 
 # ------------------------------------------------------------------------------------
@@ -1127,7 +1152,7 @@ def run_rank(args):
     K, W = args.steps, args.warmup
     if args.profile_steps > 0:
         kernel_instr_per_term()         # host-only, cached: not between the profile phase and the timed steps
-    models = ['lsm', 'hdp', 'cc', 'ccu'] if args.model == 'all' else [args.model]
+    models = args.workloads
     lines = []
     dumped = {}
     def run_model(name, args=args):

@@ -24,6 +24,6 @@ python3 $ROOT/profiles/pipe_roles.py $OUT/stats_$MODEL/bench_kernel_trace.csv > 
 find $OUT/stats_$MODEL -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats_$MODEL.csv
 fi
 if [ "$WHAT" = "bench" ] || [ "$WHAT" = "all" ]; then
-python3 $ROOT/bench.py --model $MODEL > $OUT/bench_$MODEL.json 2> $OUT/bench_$MODEL.err
+python3 $ROOT/bench.py --model $MODEL --full > $OUT/bench_$MODEL.json 2> $OUT/bench_$MODEL.err
 tail -1 $OUT/bench_$MODEL.json
 fi

@@ -100,7 +100,7 @@ def test_bench_launches_two_ranks_by_itself():
     packed network, both chains run, the results are gathered; config 5's workload
     (HDP-LPCM chains) rides along as extra_configs"""
     line = _run_bench('--gpus', '2', '--backend', 'gloo', '--share-device0', '--steps', '5',
-                      '--warmup', '2', '--profile-steps', '0', '--no-cpu', '--model', 'all')
+                      '--warmup', '2', '--profile-steps', '0', '--no-cpu', '--model', 'all', '--full')
     assert line['n_gpus'] == 2 and line['steps'] == 5 and line['scaling'] == 'weak'
     assert line['config']['chains'] == 2 and 'DynamicNetworkLSM' in line['config']['workload']
     assert line['value'] > 0 and line['dtype'] == 'f64'
@@ -117,7 +117,7 @@ def test_bench_launches_two_ranks_by_itself():
 
 
 def test_bench_single_gpu_line_has_the_contract_fields():
-    line = _run_bench('--steps', '20', '--warmup', '5', '--profile-steps', '5', '--cpu-iters', '1',
+    line = _run_bench('--full', '--steps', '20', '--warmup', '5', '--profile-steps', '5', '--cpu-iters', '1',
                       '--model', 'lsm')
     assert line['n_gpus'] == 1 and line['metric'].startswith('Gibbs iterations/sec')
     r = line['roofline']

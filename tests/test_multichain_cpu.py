@@ -126,6 +126,27 @@ def test_bench_self_launch_propagates_rank_failure():
     assert b'"metric"' not in p.stdout
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """a plain `bench.py` measures the headline configuration only: no other configuration, no per-kernel
+    profile, no CPU baseline; `--full` brings them all back, and an option given explicitly holds either way.
+    `--dump-outputs` without `--model` runs the workloads whose outputs the default run of `--full` writes"""
+    sys.path.insert(0, ROOT)
+    import bench
+    every = ['lsm', 'hdp', 'cc', 'ccu']
+    a = bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert not a.full and (a.model, a.profile_steps, a.cpu_iters, a.workloads) == ('lsm', 0, 0, ['lsm'])
+    a = bench.parse(['--full'])
+    assert a.full and (a.model, a.profile_steps, a.cpu_iters, a.workloads) == ('all', 100, 8, every)
+    a = bench.parse(['--full', '--model', 'hdp', '--profile-steps', '0'])
+    assert (a.model, a.profile_steps, a.cpu_iters, a.workloads) == ('hdp', 0, 8, ['hdp'])
+    a = bench.parse(['--model', 'all', '--cpu-iters', '1'])
+    assert (a.model, a.profile_steps, a.cpu_iters, a.workloads) == ('all', 0, 1, every)
+    # --dump-outputs writes what every workload of the default --full run computes, plain or not
+    a = bench.parse(['--dump-outputs', 'out'])
+    assert (a.model, a.profile_steps, a.cpu_iters, a.workloads) == ('lsm', 0, 0, every)
+    assert bench.parse(['--dump-outputs', 'out', '--model', 'cc']).workloads == ['cc']
+
+
 def test_fit_chains_spawns_its_ranks_and_gathers(tmp_path):
     """multichain.fit_chains from a plain process: one child per chain (gloo, world size 2), the
     network from rank 0 (a missing dyad included), chain ids and seeds offset by the rank, traces and
