@@ -13,8 +13,10 @@ from .lpcm import DynamicNetworkLPCM  # noqa
 from .case_control import DirectedCaseControlSampler  # noqa
 from . import metrics  # noqa
 from .gof import posterior_predictive_check, GofResult  # noqa
+from .ic import information_criteria, compare_information_criteria, ICResult  # noqa
 
 __version__ = '0.1.0'
 __all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
            'DynamicNetworkLSM', 'DynamicNetworkHDPLPCM', 'DynamicNetworkLPCM',
-           'DirectedCaseControlSampler', 'posterior_predictive_check', 'GofResult']
+           'DirectedCaseControlSampler', 'posterior_predictive_check', 'GofResult',
+           'information_criteria', 'compare_information_criteria', 'ICResult']

@@ -30,6 +30,7 @@
 #include "kernels_post.hpp"
 #include "kernels_forecast.hpp"
 #include "kernels_gof.hpp"
+#include "kernels_ic.hpp"
 #include "host_draws.hpp"
 
 using namespace dlsm;
@@ -2183,6 +2184,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_post.hpp"
 #include "capi_forecast.hpp"
 #include "capi_gof.hpp"
+#include "capi_ic.hpp"
 #include "capi_hdp.hpp"
 
 extern "C" int dlsm_host_sample_tables(void *numpy_bitgen, int T, int K, const double *n,

@@ -732,6 +732,41 @@ class Chain(object):
         self._ck(self._L.dlsm_gof_observed(self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(stats)))
         return stats
 
+    # -- information criteria (no reference counterpart) ---------------------------------------
+    def ic_accumulate(self, bits, Xs, intercepts, radii=None, want_pointwise=False):
+        """Pointwise log-likelihood of the packed network ``bits`` (T, N, W) uint32 (``pack_network``)
+        over the S posterior samples ``Xs`` (S, T, N, D), ``intercepts`` (S,) or (S, 2), ``radii`` (S, N)
+        (directed and case-control chains), reduced on the device (csrc/kernels_ic.hpp).  Returns
+        ``totals`` (T, 5) - per time step sum lppd, sum var, sum mean, sum (lppd - var)^2, dyads - and
+        ``sample_loglik`` (S, T), the network log-likelihood of each sample; ``want_pointwise``: also
+        (T, N, N, 2), (lppd, var) per dyad (undirected: i < j filled, the rest 0)."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        if bits.shape != (self.T, self.N, packed_row_words(self.N)):
+            raise ValueError('bits has shape %s, expected %s'
+                             % (bits.shape, (self.T, self.N, packed_row_words(self.N))))
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        S = Xs.shape[0]
+        if S < 1:
+            raise ValueError('needs at least one sample')
+        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
+        b = np.asarray(intercepts, dtype=np.float64)
+        if b.ndim == 1 and self.model == UNDIRECTED:
+            b = np.stack([b, np.zeros_like(b)], axis=1)
+        b = _f64(b, (S, 2), 'intercepts')
+        if self.model == UNDIRECTED:
+            r = None
+        else:
+            if radii is None:
+                raise ValueError('directed models need radii')
+            r = _f64(radii, (S, self.N), 'radii')
+        totals = np.zeros((self.T, 5))
+        sample_loglik = np.zeros((S, self.T))
+        pw = np.zeros((self.T, self.N, self.N, 2)) if want_pointwise else None
+        self._ck(self._L.dlsm_ic_accumulate(
+            self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(Xs), _p(b), _p(r) if r is not None else None,
+            int(S), _p(totals), _p(sample_loglik), _p(pw) if want_pointwise else None))
+        return (totals, sample_loglik, pw) if want_pointwise else (totals, sample_loglik)
+
     def profile_enable(self, on=True):
         self._ck(self._L.dlsm_profile_enable(self._h, int(on)))
 

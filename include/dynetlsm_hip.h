@@ -403,6 +403,23 @@ int dlsm_gof_simulate(dlsm_chain *h, const double *Xs, const double *intercepts,
  * bit -> DLSM_E_DATA. */
 int dlsm_gof_observed(dlsm_chain *h, const uint32_t *bits, int64_t *stats);
 
+/* ---- information criteria (WAIC, DIC) ----------------------------------- */
+/* No reference counterpart.  The pointwise log-likelihood l_s = y eta_s - log(1 + exp(eta_s)) of every
+ * dyad of the packed network `bits` (T*N*W uint32 as dlsm_gof_observed takes it; undirected handles: t,
+ * i < j; directed and case-control handles: t, i != j, the exact model of metrics.py:57-60) at the S
+ * samples Xs S*T*N*D, intercepts S*2, radii S*N (directed) or NULL, reduced over s in one pass:
+ * lppd = log mean_s exp(l_s) (streaming log-sum-exp), var = the sample variance of l_s (Welford; 0 for
+ * S = 1), mean = mean_s l_s.
+ *   totals        T*5: per time step sum lppd, sum var, sum mean, sum (lppd - var)^2, number of dyads
+ *   sample_loglik S*T: sum over the dyads of l_s - the network log-likelihood of sample s at time t
+ *   pointwise     NULL or T*N*N*2: (lppd, var) of dyad (t, i, j); undirected: i < j filled, the rest 0
+ * Every sum is taken in a fixed order (no floating-point atomics): the same call returns the same bits.
+ * All S samples are held on the device at once; if they do not fit -> DLSM_E_LIMIT, and the message
+ * names the largest S that does.  A set diagonal or padding bit, a radius <= 0 -> DLSM_E_DATA. */
+int dlsm_ic_accumulate(dlsm_chain *h, const uint32_t *bits, const double *Xs, const double *intercepts,
+                       const double *radii, int S, double *totals, double *sample_loglik,
+                       double *pointwise);
+
 /* ---- host-stream auxiliary draws ----------------------- */
 /* sample_tables (sample_auxillary.py:6-28): m T*K*K int64 = tables per (restaurant, dish)
  * given the transition counts n T*K*K (n[0,0,:] = initial counts) and beta K.  The
