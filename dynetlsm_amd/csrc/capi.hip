@@ -40,6 +40,81 @@ static int32_t *g_fix_err_host = nullptr;       // CC_ERR_FIXPOINT's word (kerne
 static int g_fix_err_device = -1;
 static std::atomic<int> g_live_chains{0};       // handles alive in this process (capi_hdp.hpp, hdp_fork_arm)
 
+// ---------------------------------------------------------------- environment switches
+// Every switch the engine takes from the environment.  read_knobs() is the one place that reads
+// them: each C-API call that enqueues work calls it once on entry - per call, not per process: the tests switch
+// them between calls - and hands the result down inside its call record.
+namespace {
+
+int env_int(const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; }
+bool env_is(const char *name, const char *word) { const char *e = getenv(name); return e && strcmp(e, word) == 0; }
+
+struct Knobs {
+    bool cc_pass_records, cc_pass_rows;                 // DLSM_CC_PASS=records / =rows
+    bool pipe_lds;                                      // DLSM_PIPE_LDS (0: off)
+    int pipe_xserve, pipe_xbudget;                      // DLSM_PIPE_XSERVE (0 off, 2 forced), DLSM_PIPE_XBUDGET
+    int cc_helpers, cc_helper_budget;                   // DLSM_CC_HELPERS (0 off, 2 forced), DLSM_CC_HELPER_BUDGET
+    int spec_s;                                         // DLSM_SPEC_S: sub-batches of algo 3
+    bool post_ride, post_fuse, tail_propose, hdp_head;  // DLSM_POST_RIDE, _POST_FUSE, _TAIL_PROPOSE, _HDP_HEAD (0: off)
+    bool graph;                                         // DLSM_GRAPH (1: on)
+    int hdp_queues, hdp_fork_budget;                    // DLSM_HDP_QUEUES (1 off, 2 forced), DLSM_HDP_FORK_BUDGET
+    bool hdp_gate_kernel;                               // DLSM_HDP_GATE=kernel
+    bool profiler;                                      // rocprofv3's tool library is loaded into the process
+};
+
+Knobs read_knobs() {
+    Knobs k;
+    k.cc_pass_records = env_is("DLSM_CC_PASS", "records"); k.cc_pass_rows = env_is("DLSM_CC_PASS", "rows");
+    k.pipe_lds = env_int("DLSM_PIPE_LDS", 1) != 0;
+    k.pipe_xserve = env_int("DLSM_PIPE_XSERVE", 1); k.pipe_xbudget = env_int("DLSM_PIPE_XBUDGET", 1 << 22);
+    k.cc_helpers = env_int("DLSM_CC_HELPERS", 1); k.cc_helper_budget = env_int("DLSM_CC_HELPER_BUDGET", 1 << 22);
+    k.spec_s = env_int("DLSM_SPEC_S", 2);
+    k.post_ride = env_int("DLSM_POST_RIDE", 1) != 0; k.post_fuse = env_int("DLSM_POST_FUSE", 1) != 0;
+    k.tail_propose = env_int("DLSM_TAIL_PROPOSE", 1) != 0; k.hdp_head = env_int("DLSM_HDP_HEAD", 1) != 0;
+    k.graph = env_int("DLSM_GRAPH", 0) == 1;
+    k.hdp_queues = env_int("DLSM_HDP_QUEUES", 0); k.hdp_fork_budget = env_int("DLSM_HDP_FORK_BUDGET", 1 << 22);
+    k.hdp_gate_kernel = env_is("DLSM_HDP_GATE", "kernel");
+    k.profiler = getenv("ROCP_TOOL_LIBRARIES") != nullptr || getenv("ROCPROFILER_REGISTER_FORCE_LOAD") != nullptr;
+    return k;
+}
+
+// DLSM_LABELS_KERNEL=wave forces the wavefront-per-node label kernel, for measurements (once per process)
+bool labels_wave_forced() {
+    static const bool v = env_is("DLSM_LABELS_KERNEL", "wave");
+    return v;
+}
+
+// A role that makes wavefronts wait inside a launch, or a second queue: `mode == off` never, `mode == forced`
+// always, otherwise only while this is the process's one live chain (what was measured: one chain alone on its
+// device gains, chains that share it lose - or, with a poll budget, end in the sticky error)
+bool alone_or_forced(int mode, int off, int forced) {
+    return mode != off && (mode == forced || g_live_chains.load() == 1);
+}
+
+// Where a piece of a C-API call is enqueued, and the switches as the call read them on entry.  The chain's own
+// queue is h->stream; the HDP-LPCM loop puts pieces on its second queue (capi_hdp.hpp).
+struct Call {
+    hipStream_t stream;
+    Knobs knobs;
+};
+
+// One sweep over the positions (enqueue_sweep and the launch_sweep_* below it)
+struct SweepCall : Call {
+    explicit SweepCall(const Call &c) : Call(c) {}
+    // in: the undirected loops ask for the centring sums to ride in the pipelined sweep's last launch
+    // (k_pipe_last_ride; xref: the Procrustes reference or NULL) and for the proposal pass to draw the loop's
+    // intercept proposal too; head_only: the proposal pass and the first, evaluate-only launch alone - neither
+    // reads what the HDP-LPCM loop's conjugate draws produce (capi_hdp.hpp); alloc_only: size the buffers only
+    bool want_post_ride = false; const double *xref = nullptr;
+    bool draw_intercept = false, head_only = false, alloc_only = false;
+    // out: the sums rode (nwg records; jl, par: the rows the launch was still moving), and a pipelined sweep
+    // left proposal buffers a later launch can fill (h->carry.next_prop)
+    bool rode = false; int nwg = 0, jl = -1, par = 0;
+    bool left_proposals = false;
+};
+
+}  // namespace
+
 #define FAIL(h, code, ...)                                      \
     do {                                                        \
         char _b[512];                                           \
@@ -100,16 +175,17 @@ static void drop_graph(dlsm_chain *h) {
 namespace {
 
 struct ProfScope {
-    dlsm_chain *h; int k; hipEvent_t e0 = nullptr, e1 = nullptr;
-    ProfScope(dlsm_chain *h_, int k_) : h(h_), k(k_) {
+    dlsm_chain *h; int k; hipStream_t q; hipEvent_t e0 = nullptr, e1 = nullptr;
+    ProfScope(dlsm_chain *h_, int k_) : ProfScope(h_, k_, h_->stream) {}
+    ProfScope(dlsm_chain *h_, int k_, hipStream_t q_) : h(h_), k(k_), q(q_) {
         if (h->profiling) {
             hipEventCreate(&e0); hipEventCreate(&e1);
-            hipEventRecord(e0, h->stream);
+            hipEventRecord(e0, q);
         }
     }
     ~ProfScope() {
         if (h->profiling) {
-            hipEventRecord(e1, h->stream);
+            hipEventRecord(e1, q);
             h->prof[k].pending.emplace_back(e0, e1);
         }
     }
@@ -226,9 +302,9 @@ int check_ready_loglik(dlsm_chain *h) {
 }
 
 // Case-control model: the valid controls per node and direction (k_count_controls) and the nodes' term rows
-// (cc_rows.hpp), rebuilt on the chain's stream when the edge tables or the controls have changed (upload /
+// (cc_rows.hpp), rebuilt on queue `q` when the edge tables or the controls have changed (upload /
 // set / resample clear the two flags).  alloc_only: buffers only (configure calls).
-static int ensure_cc_rows(dlsm_chain *h, bool alloc_only = false) {
+static int ensure_cc_rows(dlsm_chain *h, hipStream_t q, bool alloc_only = false) {
     const size_t TN = (size_t)h->T * h->N;
     if (h->nctrl_cap < TN * 2) {
         if (h->nctrl) hipFree(h->nctrl);
@@ -268,15 +344,15 @@ static int ensure_cc_rows(dlsm_chain *h, bool alloc_only = false) {
     if (alloc_only) return DLSM_OK;
     if (!h->nctrl_valid) {      // the control lists change only in set / resample
         hipLaunchKernelGGL(k_count_controls, dim3((unsigned)((TN + 255) / 256)), dim3(256),
-                           0, h->stream, h->ctrl_in, h->ctrl_out, (long)TN, h->C, h->nctrl);
+                           0, q, h->ctrl_in, h->ctrl_out, (long)TN, h->C, h->nctrl);
         h->nctrl_valid = true; h->cc_terms_valid = false;
     }
     if (!h->cc_terms_valid) {
         hipLaunchKernelGGL(k_cc_pos, dim3((unsigned)((h->N + CC_SORT_B - 1) / CC_SORT_B), (unsigned)h->T),
-                           dim3(CC_SORT_B), 0, h->stream, h->view(), h->nctrl, h->cc_pos);
-        hipLaunchKernelGGL(k_cc_rows, dim3((unsigned)((TN + 3) / 4)), dim3(256), 0, h->stream, h->view(),
+                           dim3(CC_SORT_B), 0, q, h->view(), h->nctrl, h->cc_pos);
+        hipLaunchKernelGGL(k_cc_rows, dim3((unsigned)((TN + 3) / 4)), dim3(256), 0, q, h->view(),
                            h->nctrl, h->cc_pos, h->cc_terms, tw);
-        hipLaunchKernelGGL(k_cc_order, dim3((unsigned)((h->N + 255) / 256), (unsigned)h->T), dim3(256), 0, h->stream,
+        hipLaunchKernelGGL(k_cc_order, dim3((unsigned)((h->N + 255) / 256), (unsigned)h->T), dim3(256), 0, q,
                            h->view(), h->nctrl, h->cc_pos, h->cc_emax, h->cc_order, h->cc_order_cnt);
         h->cc_terms_valid = true;
     }
@@ -303,7 +379,7 @@ int ensure_xr(dlsm_chain *h) {
 // The streaming case-control pass: as many workgroups per slice as stay resident together (occupancy query, once
 // per instantiation), trimmed so that every wavefront walks the same number of row pairs.
 template <int DD, int M, bool TWO, int PD, int NT>
-int launch_ccs(dlsm_chain *h, const ChainView &v, const LoglikCand &cand, int rslot, int *nrec_out) {
+int launch_ccs(dlsm_chain *h, hipStream_t q, const ChainView &v, const LoglikCand &cand, int rslot, int *nrec_out) {
     constexpr bool IR = NT == 1024;         // reciprocal radii in LDS: one workgroup per CU
     constexpr int NWV = NT / 64;
     const size_t lds = (size_t)(EXPTAB_N + NWV * 4 + (IR ? h->N : 0)) * sizeof(double);
@@ -315,8 +391,6 @@ int launch_ccs(dlsm_chain *h, const ChainView &v, const LoglikCand &cand, int rs
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k_loglik_casecontrol_stream<DD, M, TWO, PD, NT>,
                                                                     NT, lds);
         if (e != hipSuccess || nblk < 1) { (void)hipGetLastError(); nblk = IR ? 1 : 2; }
-        const char *eo = getenv("DLSM_CC_PASS_WG_PER_CU");     // (experiments)
-        if (eo && atoi(eo) > 0) nblk = atoi(eo);
         bpc = nblk;
     }
     const int N = h->N, T = h->T;
@@ -324,39 +398,40 @@ int launch_ccs(dlsm_chain *h, const ChainView &v, const LoglikCand &cand, int rs
     // contiguous shares; the grid is trimmed so that the shares are whole numbers of entries, near enough)
     const int wps = ccs_workgroups_per_slice(N, T, h->n_cu, bpc, NWV, (N + LLCC_NODES - 1) / LLCC_NODES);   // (cap: ll_blocks)
     hipLaunchKernelGGL((k_loglik_casecontrol_stream<DD, M, TWO, PD, NT>), dim3((unsigned)wps, (unsigned)T),
-                       dim3(NT), lds, h->stream, v, cand, h->xr, h->cc_terms, h->cc_tw, h->cc_order,
+                       dim3(NT), lds, q, v, cand, h->xr, h->cc_terms, h->cc_tw, h->cc_order,
                        h->cc_order_cnt, h->cc_emax, h->partials, rslot);
     *nrec_out = wps * T;
     return DLSM_OK;
 }
 template <int DD>
-int launch_loglik_ccstream(dlsm_chain *h, int M, bool two, const ChainView &v, const LoglikCand &cand, int rslot,
-                           int *nrec_out) {
+int launch_loglik_ccstream(dlsm_chain *h, const Call &c, int M, bool two, const ChainView &v, const LoglikCand &cand,
+                           int rslot, int *nrec_out) {
+    hipStream_t q = c.stream;
     // one radius per node (every pass but the two-radii form) and the reciprocals fit a CU's LDS: positions alone
     // are gathered (DLSM_CC_PASS=records keeps the gathered records)
-    const bool ir = !two && (size_t)h->N * sizeof(double) <= 150 * 1024 &&
-                    !(getenv("DLSM_CC_PASS") && strcmp(getenv("DLSM_CC_PASS"), "records") == 0);
+    const bool ir = !two && (size_t)h->N * sizeof(double) <= 150 * 1024 && !c.knobs.cc_pass_records;
     // (d <= 3: beyond it a position is as many requests as a record, and the 16-wavefront workgroup's 128 registers
     // no longer hold two entries of d doubles per term)
     if constexpr (DD <= 3) {
         if (ir) {
-            if (M == 1) return launch_ccs<DD, 1, false, 2, 1024>(h, v, cand, rslot, nrec_out);
-            if (M == 4) return launch_ccs<DD, 4, false, 1, 1024>(h, v, cand, 0, nrec_out);
-            return launch_ccs<DD, 2, false, 1, 1024>(h, v, cand, 0, nrec_out);
+            if (M == 1) return launch_ccs<DD, 1, false, 2, 1024>(h, q, v, cand, rslot, nrec_out);
+            if (M == 4) return launch_ccs<DD, 4, false, 1, 1024>(h, q, v, cand, 0, nrec_out);
+            return launch_ccs<DD, 2, false, 1, 1024>(h, q, v, cand, 0, nrec_out);
         }
     }
-    if (M == 1) return launch_ccs<DD, 1, false, 1, LLCS_THREADS>(h, v, cand, rslot, nrec_out);
-    if (M == 4) return launch_ccs<DD, 4, false, 1, LLCS_THREADS>(h, v, cand, 0, nrec_out);
-    if (two) return launch_ccs<DD, 2, true, 1, LLCS_THREADS>(h, v, cand, 0, nrec_out);
-    return launch_ccs<DD, 2, false, 1, LLCS_THREADS>(h, v, cand, 0, nrec_out);
+    if (M == 1) return launch_ccs<DD, 1, false, 1, LLCS_THREADS>(h, q, v, cand, rslot, nrec_out);
+    if (M == 4) return launch_ccs<DD, 4, false, 1, LLCS_THREADS>(h, q, v, cand, 0, nrec_out);
+    if (two) return launch_ccs<DD, 2, true, 1, LLCS_THREADS>(h, q, v, cand, 0, nrec_out);
+    return launch_ccs<DD, 2, false, 1, LLCS_THREADS>(h, q, v, cand, 0, nrec_out);
 }
 
 // Enqueue the log-likelihood record kernel for M candidates whose intercepts
-// are at device address `d_ic` (and radii r0 / r1); returns the record count.
+// are at device address `d_ic` (and radii r0 / r1) on the call's queue; returns the record count.
+// beside_chain: the pass runs beside the chain's own launches (the HDP-LPCM loop's second queue)
 // reuse_pack: the records are those this pass needs already (the caller knows); rslot: which of
 // a record's two radii a single candidate reads
 template <int DD>
-int launch_loglik_records(dlsm_chain *h, int M, const double *d_ic,
+int launch_loglik_records(dlsm_chain *h, const Call &c, bool beside_chain, int M, const double *d_ic,
                           const double *r0, const double *r1, int *nrec_out,
                           bool reuse_pack = false, int rslot = 0) {
     const int nb = ll_blocks(h);
@@ -364,14 +439,15 @@ int launch_loglik_records(dlsm_chain *h, int M, const double *d_ic,
     if (rc) return rc;
     ChainView v = h->view();
     LoglikCand cand{d_ic, {r0, r1}};
-    ProfScope ps(h, DLSM_K_LOGLIK);
+    hipStream_t q = c.stream;
+    ProfScope ps(h, DLSM_K_LOGLIK, q);
     if (h->model == DLSM_UNDIRECTED) {
-        const int prio = h->ll_beside_chain ? 0 : 1;      // (issue priority by progress, unless the chain's launches run beside)
-        if (M == 1) hipLaunchKernelGGL((k_loglik_undirected<DD, 1>), dim3(nb), dim3(LLU_THREADS), 0, h->stream, v, cand, h->partials, prio);
-        else hipLaunchKernelGGL((k_loglik_undirected<DD, 2>), dim3(nb), dim3(LLU_THREADS), 0, h->stream, v, cand, h->partials, prio);
+        const int prio = beside_chain ? 0 : 1;      // (issue priority by progress, unless the chain's launches run beside)
+        if (M == 1) hipLaunchKernelGGL((k_loglik_undirected<DD, 1>), dim3(nb), dim3(LLU_THREADS), 0, q, v, cand, h->partials, prio);
+        else hipLaunchKernelGGL((k_loglik_undirected<DD, 2>), dim3(nb), dim3(LLU_THREADS), 0, q, v, cand, h->partials, prio);
     } else if (h->model == DLSM_DIRECTED) {
-        if (M == 1) hipLaunchKernelGGL((k_loglik_directed<DD, 1>), dim3(nb), dim3(LL_THREADS), 0, h->stream, v, cand, h->partials);
-        else hipLaunchKernelGGL((k_loglik_directed<DD, 2>), dim3(nb), dim3(LL_THREADS), 0, h->stream, v, cand, h->partials);
+        if (M == 1) hipLaunchKernelGGL((k_loglik_directed<DD, 1>), dim3(nb), dim3(LL_THREADS), 0, q, v, cand, h->partials);
+        else hipLaunchKernelGGL((k_loglik_directed<DD, 2>), dim3(nb), dim3(LL_THREADS), 0, q, v, cand, h->partials);
     } else {
         // (the pass gathers records as 32-bit lane offsets from a slice's base: umul24 of the node)
         if (h->N >= (1 << 24) || (double)h->N * llcc_record_width(DD) * sizeof(double) >= 4294967296.0)
@@ -382,33 +458,26 @@ int launch_loglik_records(dlsm_chain *h, int M, const double *d_ic,
             int rc2 = ensure_xr<DD>(h); if (rc2) return rc2;
             if (!reuse_pack)
                 hipLaunchKernelGGL((k_pack_xr<DD>), dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0,
-                                   h->stream, h->X, r0, M > 1 ? r1 : r0, (long)nodes, h->N, h->xr);
+                                   q, h->X, r0, M > 1 ? r1 : r0, (long)nodes, h->N, h->xr);
         }
         // out-edges and out-controls as dense 64-term trips from the node's row (cc_rows.hpp)
-        { int rc3 = ensure_cc_rows(h); if (rc3) return rc3; }
+        { int rc3 = ensure_cc_rows(h, q); if (rc3) return rc3; }
         // (round 6: a resident wave of streaming wavefronts - kernels_loglik_ccstream.hpp; DLSM_CC_PASS=rows keeps
         // the two-rows-per-wavefront form)
         // (k_cc_order ranks by out_deg * 65536 + n_out_controls in 32 bits: lists beyond that keep the rows form)
-        const bool stream_form = !(getenv("DLSM_CC_PASS") && strcmp(getenv("DLSM_CC_PASS"), "rows") == 0) &&
-                                 cc_order_key_holds(h->Dout, h->C);
+        const bool stream_form = !c.knobs.cc_pass_rows && cc_order_key_holds(h->Dout, h->C);
         if (stream_form) {
             const bool two = M == 2 && r1 != r0;
-            int rc4 = launch_loglik_ccstream<DD>(h, M, two, v, cand, rslot, nrec_out); if (rc4) return rc4;
+            int rc4 = launch_loglik_ccstream<DD>(h, c, M, two, v, cand, rslot, nrec_out); if (rc4) return rc4;
             HIPCHK(h, hipGetLastError());
             return DLSM_OK;
         }
-        if (M == 1) hipLaunchKernelGGL((k_loglik_casecontrol_rows<DD, 1>), dim3(nb / h->T, h->T), dim3(LLCR_THREADS), 0, h->stream, v, cand, h->xr, h->cc_terms, h->cc_tw, h->partials, rslot);
-        else if (M == 4) hipLaunchKernelGGL((k_loglik_casecontrol_rows<DD, 4>), dim3(nb / h->T, h->T), dim3(LLCR_THREADS), 0, h->stream, v, cand, h->xr, h->cc_terms, h->cc_tw, h->partials, 0);
-        else hipLaunchKernelGGL((k_loglik_casecontrol_rows<DD, 2>), dim3(nb / h->T, h->T), dim3(LLCR_THREADS), 0, h->stream, v, cand, h->xr, h->cc_terms, h->cc_tw, h->partials, 0);
+        if (M == 1) hipLaunchKernelGGL((k_loglik_casecontrol_rows<DD, 1>), dim3(nb / h->T, h->T), dim3(LLCR_THREADS), 0, q, v, cand, h->xr, h->cc_terms, h->cc_tw, h->partials, rslot);
+        else if (M == 4) hipLaunchKernelGGL((k_loglik_casecontrol_rows<DD, 4>), dim3(nb / h->T, h->T), dim3(LLCR_THREADS), 0, q, v, cand, h->xr, h->cc_terms, h->cc_tw, h->partials, 0);
+        else hipLaunchKernelGGL((k_loglik_casecontrol_rows<DD, 2>), dim3(nb / h->T, h->T), dim3(LLCR_THREADS), 0, q, v, cand, h->xr, h->cc_terms, h->cc_tw, h->partials, 0);
     }
     HIPCHK(h, hipGetLastError());
     *nrec_out = nb;
-    return DLSM_OK;
-}
-
-int loglik_records(dlsm_chain *h, int M, const double *d_ic, const double *r0,
-                   const double *r1, int *nrec, bool reuse_pack = false, int rslot = 0) {
-    DISPATCH_D(h, h->D, return launch_loglik_records<DD>(h, M, d_ic, r0, r1, nrec, reuse_pack, rslot));
     return DLSM_OK;
 }
 
@@ -542,9 +611,6 @@ void dlsm_destroy(dlsm_chain *h) {
     if (h->hsmall) hipHostFree(h->hsmall);
     if (h->timer0) hipEventDestroy(h->timer0);
     if (h->timer1) hipEventDestroy(h->timer1);
-    if (h->ev_a) hipEventDestroy(h->ev_a);
-    if (h->ev_b) hipEventDestroy(h->ev_b);
-    if (h->stream2) { hipStreamSynchronize(h->stream2); hipStreamDestroy(h->stream2); }
     if (h->fork_stream) { hipStreamSynchronize(h->fork_stream); hipStreamDestroy(h->fork_stream); }
     if (h->fork_ev) hipEventDestroy(h->fork_ev);
     if (h->fork_flags) hipFree(h->fork_flags);
@@ -906,6 +972,7 @@ int dlsm_loglik_full(dlsm_chain *h, int m, const double *intercepts, double *out
     int rc = check_ready_loglik(h); if (rc) return rc;
     const int nic = h->model == DLSM_UNDIRECTED ? 1 : 2;
     if (!intercepts) NEED(h, m == 1, "intercepts == NULL requires m == 1");
+    const Call call{h->stream, read_knobs()};
     for (int k0 = 0; k0 < m; k0 += 2) {
         const int M = std::min(2, m - k0);
         const double *d_ic = h->intercept;
@@ -916,7 +983,8 @@ int dlsm_loglik_full(dlsm_chain *h, int m, const double *intercepts, double *out
             d_ic = h->dsmall;
         }
         int nrec = 0;
-        rc = loglik_records(h, M, d_ic, h->radii, h->radii, &nrec); if (rc) return rc;
+        DISPATCH_D(h, h->D, rc = launch_loglik_records<DD>(h, call, false, M, d_ic, h->radii, h->radii, &nrec));
+        if (rc) return rc;
         hipLaunchKernelGGL(k_reduce_loglik, dim3(1), dim3(256), 0, h->stream, h->partials,
                            nrec, h->model, M, d_ic, h->dsmall + 16);
         HIPCHK(h, hipGetLastError());
@@ -940,7 +1008,9 @@ int dlsm_loglik_full_radii(dlsm_chain *h, const double *radii_alt, double *out) 
     HIPCHK(h, hipMemcpyAsync(h->dsmall + 2, h->intercept, 2 * sizeof(double),
                              hipMemcpyDeviceToDevice, h->stream));
     int nrec = 0;
-    rc = loglik_records(h, 2, h->dsmall, h->radii, h->radii_alt, &nrec); if (rc) return rc;
+    const Call call{h->stream, read_knobs()};
+    DISPATCH_D(h, h->D, rc = launch_loglik_records<DD>(h, call, false, 2, h->dsmall, h->radii, h->radii_alt, &nrec));
+    if (rc) return rc;
     hipLaunchKernelGGL(k_reduce_loglik, dim3(1), dim3(256), 0, h->stream, h->partials, nrec,
                        h->model, 2, h->dsmall, h->dsmall + 16);
     HIPCHK(h, hipGetLastError());
@@ -1022,14 +1092,14 @@ static void launch_spec_eval(dlsm_chain *h, const ChainView &v, const SpecBuf &s
 }
 
 template <int DD>
-static int launch_sweep_spec(dlsm_chain *h, IterRef iter, int S, bool alloc_only = false) {
+static int launch_sweep_spec(dlsm_chain *h, const SweepCall &sc, IterRef iter, int S) {
     const int N = h->N, T = h->T;
+    hipStream_t q = sc.stream;
     if (h->model == DLSM_DIRECTED_CASE_CONTROL) S = 1;          // one wave per node there
     S = std::max(1, std::min(S, SP_SMAX));
     const int B = std::min(S * SP_BMAX, (N + 1) / 2 * 2);       // even: double2 staging
     const int nsl_max = (T + 1) / 2;
     int parts = (1024 + nsl_max * SP_BMAX - 1) / (nsl_max * SP_BMAX);
-    if (getenv("DLSM_SPEC_PARTS")) parts = atoi(getenv("DLSM_SPEC_PARTS"));
     parts = std::max(1, std::min(parts, 8));
     if (h->model == DLSM_DIRECTED_CASE_CONTROL) parts = 1;
     auto even2 = [](size_t n) { return (n + 1) / 2 * 2; };
@@ -1053,74 +1123,36 @@ static int launch_sweep_spec(dlsm_chain *h, IterRef iter, int S, bool alloc_only
     const size_t lds = (size_t)SP_BMAX * SP_BMAX * sizeof(double);
     HIPCHK(h, hipFuncSetAttribute((const void *)resolve,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (alloc_only) return DLSM_OK;
-    // The slices of a parity are independent, so they can be split over two queues to
-    // let one group's resolve overlap the other group's eval.  Measured on MI355X this
-    // buys nothing at N=2000 (twice the launches: host bound) and 3.6 % at N=4000 (the
-    // 16-wave resolve workgroup is not placed while eval saturates the CUs), so it is
-    // opt-in: DLSM_SPEC_QUEUES=2.
-    int nq = (getenv("DLSM_SPEC_QUEUES") ? atoi(getenv("DLSM_SPEC_QUEUES")) : 1);
-    if (h->profiling || nsl_max < 2) nq = 1;
-    if (nq > 1 && !h->stream2) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_a, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_b, hipEventDisableTiming));
-    }
-    hipStream_t qs[2] = {h->stream, nq > 1 ? h->stream2 : h->stream};
-    if (nq > 1) {       // fork
-        HIPCHK(h, hipEventRecord(h->ev_a, h->stream));
-        HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_a, 0));
-    }
+    if (sc.alloc_only) return DLSM_OK;
+    // (the slices of a parity split over two queues, one group's resolve beside the other's eval, bought nothing
+    // at N=2000 and 3.6 % at N=4000, where the pipelined sweep is the default: removed)
     for (int parity = 0; parity < 2; ++parity) {
         const int nsl = (T - parity + 1) / 2;
         if (nsl <= 0) continue;
-        const int ng = (nq > 1 && nsl >= 2) ? 2 : 1;
-        const int first[3] = {0, ng == 2 ? (nsl + 1) / 2 : nsl, nsl};
-        for (int g = 0; g < ng; ++g) {
-            SpecBuf sg = sb; sg.s0 = first[g];
-            hipLaunchKernelGGL((k_spec_propose<DD>), dim3((N + 255) / 256, first[g + 1] - first[g]),
-                               dim3(256), 0, qs[g], v, sg, iter, parity);
-        }
+        hipLaunchKernelGGL((k_spec_propose<DD>), dim3((N + 255) / 256, nsl), dim3(256), 0, q, v, sb, iter, parity);
         for (int j0 = 0; j0 < N; j0 += B) {
             const int nsb = std::min(B, N - j0);
-            for (int g = 0; g < ng; ++g) {
-                SpecBuf sg = sb; sg.s0 = first[g];
-                const int ns = first[g + 1] - first[g];
-                const size_t nblk = (size_t)parts * nsb * ns;
-                if (h->profiling && h->stamps && h->model != DLSM_DIRECTED_CASE_CONTROL &&
-                    h->stamps_used + nblk <= h->stamps_cap) {
-                    sg.stamps = h->stamps + 2 * h->stamps_used;
-                    h->stamp_launches.emplace_back(h->stamps_used, nblk);
-                    h->stamps_used += nblk;
-                }
-                {
-                    if (h->model == DLSM_DIRECTED_CASE_CONTROL) {
-                        ProfScope pe(h, DLSM_K_SWEEP_EVAL);
-                        hipLaunchKernelGGL((k_spec_eval_cc<DD>), dim3((unsigned)(ns * nsb)),
-                                           dim3(64), 0, qs[g], v, sg, h->nctrl, parity, j0, nsb);
-                    } else if (S == 1)
-                        launch_spec_eval<DD, SP_BMAX>(h, v, sg, dim3(parts, nsb, ns), qs[g],
-                                                      parity, j0, nsb);
-                    else if (S == 2)
-                        launch_spec_eval<DD, 2 * SP_BMAX>(h, v, sg, dim3(parts, nsb, ns), qs[g],
-                                                          parity, j0, nsb);
-                    else
-                        launch_spec_eval<DD, SP_SMAX * SP_BMAX>(h, v, sg, dim3(parts, nsb, ns),
-                                                                qs[g], parity, j0, nsb);
-                }
-                {
-                    ProfScope pr(h, DLSM_K_SWEEP_RESOLVE);
-                    hipLaunchKernelGGL(resolve, dim3(ns), dim3(SP_RES_THREADS), lds, qs[g], v, sg,
-                                       parity, j0, nsb);
-                }
+            SpecBuf sg = sb;
+            const size_t nblk = (size_t)parts * nsb * nsl;
+            if (h->profiling && h->stamps && h->model != DLSM_DIRECTED_CASE_CONTROL &&
+                h->stamps_used + nblk <= h->stamps_cap) {
+                sg.stamps = h->stamps + 2 * h->stamps_used;
+                h->stamp_launches.emplace_back(h->stamps_used, nblk);
+                h->stamps_used += nblk;
             }
-        }
-        if (nq > 1) {   // the next parity (or the caller) needs every slice of this one
-            HIPCHK(h, hipEventRecord(h->ev_b, h->stream2));
-            HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_b, 0));
-            if (parity == 0) {
-                HIPCHK(h, hipEventRecord(h->ev_a, h->stream));
-                HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_a, 0));
+            if (h->model == DLSM_DIRECTED_CASE_CONTROL) {
+                ProfScope pe(h, DLSM_K_SWEEP_EVAL, q);
+                hipLaunchKernelGGL((k_spec_eval_cc<DD>), dim3((unsigned)(nsl * nsb)),
+                                   dim3(64), 0, q, v, sg, h->nctrl, parity, j0, nsb);
+            } else if (S == 1)
+                launch_spec_eval<DD, SP_BMAX>(h, v, sg, dim3(parts, nsb, nsl), q, parity, j0, nsb);
+            else if (S == 2)
+                launch_spec_eval<DD, 2 * SP_BMAX>(h, v, sg, dim3(parts, nsb, nsl), q, parity, j0, nsb);
+            else
+                launch_spec_eval<DD, SP_SMAX * SP_BMAX>(h, v, sg, dim3(parts, nsb, nsl), q, parity, j0, nsb);
+            {
+                ProfScope pr(h, DLSM_K_SWEEP_RESOLVE, q);
+                hipLaunchKernelGGL(resolve, dim3(nsl), dim3(SP_RES_THREADS), lds, q, v, sg, parity, j0, nsb);
             }
         }
     }
@@ -1143,11 +1175,11 @@ static int resolve_sweep_algo(const dlsm_chain *h, int algo) {
 
 // algo 4: one fused launch per batch, resolve(b) beside eval(b + 1) (kernels_spec_pipe.hpp)
 template <int DD, int MODEL, int G = 1>
-static void launch_pipe_step(dlsm_chain *h, const ChainView &v, const PipeBuf &pb, dim3 grid,
+static void launch_pipe_step(dlsm_chain *h, hipStream_t q, const ChainView &v, const PipeBuf &pb, dim3 grid,
                              size_t lds, int l) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->profiling) { hipEventCreate(&e0); hipEventCreate(&e1); }
-    hipExtLaunchKernelGGL((k_pipe_step<DD, MODEL, G>), grid, dim3(PP_THREADS), lds, h->stream,
+    hipExtLaunchKernelGGL((k_pipe_step<DD, MODEL, G>), grid, dim3(PP_THREADS), lds, q,
                           e0, e1, 0, v, pb, l);
     if (h->profiling) h->prof[DLSM_K_SWEEP_EVAL].pending.emplace_back(e0, e1);
 }
@@ -1184,20 +1216,19 @@ static int check_pipe_err(dlsm_chain *h) {
 // one batch resolved (and one evaluated) per launch (the kernels' template parameter G = 1: the two-batch
 // form, algo 6, and the single persistent launch, algo 7, measured slower and were removed in round 5)
 template <int DD>
-static int launch_sweep_pipe(dlsm_chain *h, IterRef iter, bool alloc_only = false) {
+static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
     constexpr int G = 1;
+    hipStream_t q = sc.stream;
+    const Knobs &kn = sc.knobs;
     const int N = h->N, T = h->T;
     const int nbat = (N + PP_B - 1) / PP_B;
     const bool cc = h->model == DLSM_DIRECTED_CASE_CONTROL;
     int ne_wg = std::max(h->n_cu / 2, h->n_cu - T);
     int parts = (int)((double)ne_wg * PP_WAVES / ((double)T * PP_B) + 0.5);
-    if (getenv("DLSM_PIPE_PARTS")) parts = atoi(getenv("DLSM_PIPE_PARTS"));
     parts = std::max(1, std::min(parts, PP_MAXPARTS));
     // (undirected model: the evaluators of kernels_pipe_lds.hpp take ONE round of items - a part less when
     // rounding up would leave items for a second round)
-    if (h->model == DLSM_UNDIRECTED && parts > 1 && (long)parts * T * PP_B > (long)ne_wg * PP_WAVES &&
-        !getenv("DLSM_PIPE_PARTS"))
-        --parts;
+    if (h->model == DLSM_UNDIRECTED && parts > 1 && (long)parts * T * PP_B > (long)ne_wg * PP_WAVES) --parts;
     if (cc) {           // CC_PARTS wavefronts per node, four nodes per workgroup round
         parts = CC_PARTS;
         ne_wg = std::min(ne_wg, (T * PP_B * CC_PARTS + PP_WAVES - 1) / PP_WAVES);
@@ -1223,7 +1254,7 @@ static int launch_sweep_pipe(dlsm_chain *h, IterRef iter, bool alloc_only = fals
     pb.consts = pb.Hx + n_hx + n_acc;
     pb.xprod = pb.consts + 2;
     pb.sync = nullptr; pb.nsync = 0; pb.queue0 = ne_wg;
-    pb.lsm_draw = h->loop_draws_intercept ? h->lsm : nullptr;
+    pb.lsm_draw = sc.draw_intercept ? h->lsm : nullptr;
     pb.parts = parts; pb.nbat = nbat;
     pb.G = G; pb.xr = xr;
     pb.per = ((N + parts - 1) / parts + 63) / 64 * 64;      // parts start on a 64-neighbour boundary
@@ -1234,21 +1265,16 @@ static int launch_sweep_pipe(dlsm_chain *h, IterRef iter, bool alloc_only = fals
     // whenever the longest part's rows fit beside the exp table
     // and the launch's wavefronts cover its items in one round
     pb.lds_eval = h->model == DLSM_UNDIRECTED && pipe_lds_eval_bytes(N, DD, parts) <= lds &&
-                  (long)parts * T * PP_B <= (long)ne_wg * PP_WAVES &&
-                  !(getenv("DLSM_PIPE_LDS") && atoi(getenv("DLSM_PIPE_LDS")) == 0);
+                  (long)parts * T * PP_B <= (long)ne_wg * PP_WAVES && kn.pipe_lds;
     // the resolvers' cross products by the evaluators (pipe_xserve_*): one wavefront in xstride takes a row.  A
     // resolver waits INSIDE the launch for wavefronts that wait for nothing - they only have to start
-    {
-        const char *ex = getenv("DLSM_PIPE_XSERVE"), *ebud = getenv("DLSM_PIPE_XBUDGET");
-        pb.err = h->fork_err_dev;
-        pb.budget = ebud ? atoi(ebud) : (1 << 22);
-        // (one chain on the device: with several, a resolver's wait for evaluator workgroups that other chains' launches
-        // keep off the CUs costs more than the cross block - four chains: 6100 it/s served, 6970 not; DLSM_PIPE_XSERVE=2
-        // forces it)
-        pb.xserve = pb.lds_eval && pb.err != nullptr && T < 128 &&
-                    (ex ? (atoi(ex) == 2 || (atoi(ex) != 0 && g_live_chains.load() == 1)) : g_live_chains.load() == 1);
-    }
-    const int xserve_sweep = pb.xserve;         // (a launch whose workgroups cannot cover the rows keeps the resolvers' own products)
+    pb.err = h->fork_err_dev;
+    pb.budget = kn.pipe_xbudget;
+    // (one chain on the device: with several, a resolver's wait for evaluator workgroups that other chains' launches
+    // keep off the CUs costs more than the cross block - four chains: 6100 it/s served, 6970 not; DLSM_PIPE_XSERVE=2
+    // forces it, 0 switches it off)
+    // (a launch whose workgroups cannot cover the rows keeps the resolvers' own products)
+    const int xserve_sweep = pb.lds_eval && pb.err != nullptr && T < 128 && alone_or_forced(kn.pipe_xserve, 0, 2);
     pb.xserve = 0;
     ChainView v = h->view();
     {   // the evaluators' arguments (kernels_pipe_lds.hpp) in one piece
@@ -1275,16 +1301,12 @@ static int launch_sweep_pipe(dlsm_chain *h, IterRef iter, bool alloc_only = fals
                                   (int)lds));
     HIPCHK(h, hipFuncSetAttribute((const void *)k_pipe_last_ride<DD>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (alloc_only) return DLSM_OK;
+    if (sc.alloc_only) return DLSM_OK;
     {   // the proposal pass, unless the previous iteration's last launch carried it
         const ProposeBuf nb{pb.prop, pb.consts, pb.sync, pb.nsync, pb.queue0, pb.lsm_draw};
-        const bool drawn = !iter.ptr && h->prop_drawn_for == (long)iter.value && h->next_prop_ok &&
-                           h->next_prop.prop == nb.prop && h->next_prop.sync == nb.sync &&
-                           h->next_prop.queue0 == nb.queue0 && h->next_prop.lsm_draw == nb.lsm_draw;
-        if (!drawn)
-            hipLaunchKernelGGL((k_pipe_propose<DD>), dim3((N + 255) / 256, T), dim3(256), 0, h->stream, v,
-                               pb, iter);
-        h->next_prop = nb; h->next_prop_ok = true; h->prop_drawn_for = -1; h->pipe_touched = true;
+        if (!h->carry.drawn(iter.ptr ? -1L : (long)iter.value, nb))
+            hipLaunchKernelGGL((k_pipe_propose<DD>), dim3((N + 255) / 256, T), dim3(256), 0, q, v, pb, iter);
+        h->carry.taken(nb); sc.left_proposals = true;
     }
     // launch l: even slices resolve batches G l .. / evaluate G (l + 1) .., odd slices one launch
     // behind; with a single slice (T == 1) the trailing odd-only launch is empty
@@ -1293,26 +1315,25 @@ static int launch_sweep_pipe(dlsm_chain *h, IterRef iter, bool alloc_only = fals
     for (int l = -1; l <= last; ++l) {
         // (the head - the proposal pass above and launch -1 - may have been enqueued on the chain's second
         // queue already, beside the previous iteration's conjugate draws: capi_hdp.hpp)
-        if (l == -1 && !iter.ptr && h->head_done_for == (long)iter.value) continue;
-        if (h->sweep_part == 1 && l >= 0) break;
+        if (l == -1 && !iter.ptr && h->carry.head_done_for == (long)iter.value) continue;
+        if (sc.head_only && l >= 0) break;
         const bool any_eval = (G * (l + 1) < nbat) || (T > 1 && l >= 0 && G * l < nbat);
         const int grid = T + (any_eval ? ne_wg : 0);
         const bool lng = !pb.lds_eval;       // (undirected model without the LDS evaluators: pipe_eval_item's pipelined trips)
-        if (l == last && !any_eval && h->post_ride_want && G == 1 && h->model == DLSM_UNDIRECTED &&
+        if (l == last && !any_eval && sc.want_post_ride && G == 1 && h->model == DLSM_UNDIRECTED &&
             !h->profiling && l >= 0 && T + 4 <= PS_BLOCKS) {
             // the centring sums ride in the resolve-only launch (kernels_spec_pipe.hpp): nwg rider
             // records + one per slice from the resolvers
             const long rows = (long)T * N;
             const int nwg = (int)std::min<long>(PS_BLOCKS - T, (rows + PP_THREADS - 1) / PP_THREADS);
-            PipePostRide pr{h->post_ride_xref, iter, h->partials + (size_t)ll_blocks(h) * 4, nwg,
+            PipePostRide pr{sc.xref, iter, h->partials + (size_t)ll_blocks(h) * 4, nwg,
                             (nbat - 1) * PP_B, T > 1 ? 1 : 0};
-            hipLaunchKernelGGL((k_pipe_last_ride<DD>), dim3(T + nwg), dim3(PP_THREADS), lds, h->stream, v, pb,
-                               l, pr);
-            h->post_ride_done = true; h->post_ride_nwg = nwg + T; h->post_ride_jl = pr.jl; h->post_ride_par = pr.par;
+            hipLaunchKernelGGL((k_pipe_last_ride<DD>), dim3(T + nwg), dim3(PP_THREADS), lds, q, v, pb, l, pr);
+            sc.rode = true; sc.nwg = nwg + T; sc.jl = pr.jl; sc.par = pr.par;
             continue;
         }
         if (h->model == DLSM_UNDIRECTED && lng)
-            launch_pipe_step<DD, PIPE_UNDIRECTED_LONG>(h, v, pb, dim3(grid), lds, l);
+            launch_pipe_step<DD, PIPE_UNDIRECTED_LONG>(h, q, v, pb, dim3(grid), lds, l);
         else if (h->model == DLSM_UNDIRECTED && pb.lds_eval && any_eval) {
             // kernels_pipe_lds.hpp: plane 0 = the resolvers (padded to the planes' size), plane p + 1 = part p's
             // evaluators, 16 consecutive nodes (x) of one active slice (y) per workgroup
@@ -1328,13 +1349,13 @@ static int launch_sweep_pipe(dlsm_chain *h, IterRef iter, bool alloc_only = fals
             a.xstride = (T * PP_B + ne_wg - 1) / ne_wg;
             pb.xserve = a.xserve = xserve_sweep && a.xstride <= PP_WAVES;
             (void)gx;
-            launch_pipe_step<DD, DLSM_UNDIRECTED>(h, v, pb, dim3(grid), lds, l);
+            launch_pipe_step<DD, DLSM_UNDIRECTED>(h, q, v, pb, dim3(grid), lds, l);
         } else if (h->model == DLSM_UNDIRECTED)
-            launch_pipe_step<DD, DLSM_UNDIRECTED>(h, v, pb, dim3(grid), lds, l);
+            launch_pipe_step<DD, DLSM_UNDIRECTED>(h, q, v, pb, dim3(grid), lds, l);
         else if (h->model == DLSM_DIRECTED)
-            launch_pipe_step<DD, DLSM_DIRECTED>(h, v, pb, dim3(grid), lds, l);
+            launch_pipe_step<DD, DLSM_DIRECTED>(h, q, v, pb, dim3(grid), lds, l);
         else
-            launch_pipe_step<DD, DLSM_DIRECTED_CASE_CONTROL>(h, v, pb, dim3(grid), lds, l);
+            launch_pipe_step<DD, DLSM_DIRECTED_CASE_CONTROL>(h, q, v, pb, dim3(grid), lds, l);
     }
     HIPCHK(h, hipGetLastError());
     return DLSM_OK;
@@ -1343,7 +1364,8 @@ static int launch_sweep_pipe(dlsm_chain *h, IterRef iter, bool alloc_only = fals
 // algo 5: the case-control likelihood with sparse correction lists, batches of CP_B = 512 nodes
 // (kernels_ccpipe.hpp)
 template <int DD>
-static int launch_sweep_ccpipe(dlsm_chain *h, IterRef iter, bool alloc_only = false) {
+static int launch_sweep_ccpipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
+    hipStream_t q = sc.stream;
     const int N = h->N, T = h->T;
     const int nbat = (N + CP_B - 1) / CP_B;
     const int cap = std::max(1, h->Din + h->Dout + 2 * h->C);   // either list may hold every term
@@ -1371,9 +1393,9 @@ static int launch_sweep_ccpipe(dlsm_chain *h, IterRef iter, bool alloc_only = fa
         FAIL(h, DLSM_E_LIMIT, "case-control sweep (algo 5): N=%d T=%d is beyond its 32-bit gather offsets "
              "(N < 2^24, (T + 1) N record bytes < 2^32); use sweep_algo 4 or 2", N, T);
     // the nodes' term rows: rebuilt when the edge tables or the controls have changed
-    { int rc_ = ensure_cc_rows(h, alloc_only); if (rc_) return rc_; }
+    { int rc_ = ensure_cc_rows(h, q, sc.alloc_only); if (rc_) return rc_; }
     const int tw = h->cc_tw;
-    if (alloc_only) return DLSM_OK;
+    if (sc.alloc_only) return DLSM_OK;
     CcPipeBuf pb;
     pb.prop = h->pipe; pb.tot = pb.prop + n_prop; pb.xval = pb.tot + n_tot; pb.oval = pb.xval + n_ent;
     double *consts = pb.oval + n_ent;
@@ -1384,16 +1406,12 @@ static int launch_sweep_ccpipe(dlsm_chain *h, IterRef iter, bool alloc_only = fa
     // a helper workgroup per resolver (kernels_ccpipe.hpp, ccpipe_cross_helper) when the launch still fits the
     // device in one wave of workgroups - a resolver waits for its helper INSIDE the launch, so both must be
     // resident; DLSM_CC_HELPERS=0 keeps the resolvers on their own
-    const char *eh = getenv("DLSM_CC_HELPERS");
     // (one chain on the device - as hdp_fork_arm and the pipelined sweep's served cross products decide: with several
     // chains' launches on the CUs a helper may not be resident when its resolver starts to poll, and a slow but
     // correct run would end in the sticky error; DLSM_CC_HELPERS=2 forces the role, 0 switches it off)
-    pb.helpers = (eh ? (atoi(eh) == 2 || (atoi(eh) != 0 && g_live_chains.load() == 1)) : g_live_chains.load() == 1) &&
-                 h->n_cu >= 4 * T && h->fork_err_dev != nullptr;
-    {   // polls of a resolver's wait for its helper before the sticky error word is set (DLSM_CC_HELPER_BUDGET)
-        const char *ebud = getenv("DLSM_CC_HELPER_BUDGET");
-        pb.budget = ebud ? atoi(ebud) : (1 << 22);
-    }
+    pb.helpers = alone_or_forced(sc.knobs.cc_helpers, 0, 2) && h->n_cu >= 4 * T && h->fork_err_dev != nullptr;
+    // polls of a resolver's wait for its helper before the sticky error word is set (DLSM_CC_HELPER_BUDGET)
+    pb.budget = sc.knobs.cc_helper_budget;
     pb.err = h->fork_err_dev;
     pb.nctrl = h->nctrl; pb.cap = cap; pb.nbat = nbat;
     pb.terms = h->cc_terms; pb.tw = tw;
@@ -1402,15 +1420,12 @@ static int launch_sweep_ccpipe(dlsm_chain *h, IterRef iter, bool alloc_only = fa
     ChainView v = h->view();
     {   // the proposal pass, unless the previous iteration's last launch carried it
         const ProposeBuf nb{pp.prop, pp.consts, nullptr, 0, 0, nullptr};
-        const bool drawn = !iter.ptr && h->prop_drawn_for == (long)iter.value && h->next_prop_ok &&
-                           h->next_prop.prop == nb.prop && h->next_prop.sync == nullptr;
-        if (!drawn)
-            hipLaunchKernelGGL((k_pipe_propose<DD>), dim3((N + 255) / 256, T), dim3(256), 0, h->stream, v,
-                               pp, iter);
-        h->next_prop = nb; h->next_prop_ok = true; h->prop_drawn_for = -1; h->pipe_touched = true;
+        if (!h->carry.drawn(iter.ptr ? -1L : (long)iter.value, nb))
+            hipLaunchKernelGGL((k_pipe_propose<DD>), dim3((N + 255) / 256, T), dim3(256), 0, q, v, pp, iter);
+        h->carry.taken(nb); sc.left_proposals = true;
     }
     hipLaunchKernelGGL((k_ccpipe_pack<DD>), dim3((unsigned)(((size_t)T * N + 255) / 256)), dim3(256), 0,
-                       h->stream, v, pb);
+                       q, v, pb);
     const int nodes_max = ((T + 1) / 2 + T / 2) * std::min(CP_B, N);
     // one evaluator workgroup per remaining CU; the items are dealt out over all of them (kernels_ccpipe.hpp)
     const int n_front = pb.helpers ? 2 * T : T;         // resolvers (+ their helpers) in front of the evaluators
@@ -1421,7 +1436,7 @@ static int launch_sweep_ccpipe(dlsm_chain *h, IterRef iter, bool alloc_only = fa
         const int grid = n_front + (any_eval ? ne_wg : 0);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (h->profiling) { hipEventCreate(&e0); hipEventCreate(&e1); }
-        hipExtLaunchKernelGGL((k_ccpipe_step<DD>), dim3(grid), dim3(CP_THREADS), 0, h->stream, e0, e1,
+        hipExtLaunchKernelGGL((k_ccpipe_step<DD>), dim3(grid), dim3(CP_THREADS), 0, q, e0, e1,
                               0, v, pb, l);
         if (h->profiling) h->prof[DLSM_K_SWEEP_EVAL].pending.emplace_back(e0, e1);
     }
@@ -1430,47 +1445,39 @@ static int launch_sweep_ccpipe(dlsm_chain *h, IterRef iter, bool alloc_only = fa
 }
 
 template <int DD>
-static int launch_sweep(dlsm_chain *h, IterRef iter, int algo, bool alloc_only = false) {
+static int launch_sweep(dlsm_chain *h, SweepCall &sc, IterRef iter, int algo) {
     ChainView v = h->view();
-    ProfScope ps(h, DLSM_K_SWEEP);
+    hipStream_t q = sc.stream;
+    const bool alloc_only = sc.alloc_only;
+    ProfScope ps(h, DLSM_K_SWEEP, q);
     if (h->model == DLSM_DIRECTED_CASE_CONTROL) {
         // number of valid (non -1) controls per node and direction, and the nodes' term rows
-        { int rc_ = ensure_cc_rows(h, alloc_only); if (rc_) return rc_; }
+        { int rc_ = ensure_cc_rows(h, q, alloc_only); if (rc_) return rc_; }
         algo = resolve_sweep_algo(h, algo);
-        if (alloc_only) {
-            hipStreamSynchronize(h->stream);
-            if constexpr (DD <= DLSM_D_CCPIPE_MAX) {
-                if (algo == 5) return launch_sweep_ccpipe<DD>(h, iter, true);
-            }
-            if constexpr (DD <= DLSM_D_PIPE_MAX) {
-                if (algo == 4) return launch_sweep_pipe<DD>(h, iter, true);
-            }
-            return algo >= 2 ? launch_sweep_spec<DD>(h, iter, 1, true) : DLSM_OK;
-        }
+        if (alloc_only) hipStreamSynchronize(q);
         if constexpr (DD <= DLSM_D_CCPIPE_MAX) {
-            if (algo == 5) return launch_sweep_ccpipe<DD>(h, iter);
+            if (algo == 5) return launch_sweep_ccpipe<DD>(h, sc, iter);
         }
         if constexpr (DD <= DLSM_D_PIPE_MAX) {
-            if (algo == 4) return launch_sweep_pipe<DD>(h, iter);
+            if (algo == 4) return launch_sweep_pipe<DD>(h, sc, iter);
         }
-        if (algo >= 2) return launch_sweep_spec<DD>(h, iter, 1);
+        if (algo >= 2) return launch_sweep_spec<DD>(h, sc, iter, 1);
+        if (alloc_only) return DLSM_OK;
         for (int parity = 0; parity < 2; ++parity) {
             int nsl = (h->T - parity + 1) / 2;
             if (nsl <= 0) continue;
             hipLaunchKernelGGL((k_sweep_casecontrol<DD>), dim3(nsl), dim3(CC_THREADS), 0,
-                               h->stream, v, h->nctrl, iter, parity);
+                               q, v, h->nctrl, iter, parity);
         }
         HIPCHK(h, hipGetLastError());
         return DLSM_OK;
     }
     algo = resolve_sweep_algo(h, algo);
     if constexpr (DD <= DLSM_D_PIPE_MAX) {
-        if (algo == 4) return launch_sweep_pipe<DD>(h, iter, alloc_only);
+        if (algo == 4) return launch_sweep_pipe<DD>(h, sc, iter);
     }
-    if (algo == 2) return launch_sweep_spec<DD>(h, iter, 1, alloc_only);
-    if (algo == 3)
-        return launch_sweep_spec<DD>(h, iter, getenv("DLSM_SPEC_S") ? atoi(getenv("DLSM_SPEC_S")) : 2,
-                                     alloc_only);
+    if (algo == 2) return launch_sweep_spec<DD>(h, sc, iter, 1);
+    if (algo == 3) return launch_sweep_spec<DD>(h, sc, iter, sc.knobs.spec_s);
     const size_t lds = sweep_slice_lds_bytes(h->N, DD, h->W, h->model);
     if (lds > 160 * 1024)
         FAIL(h, DLSM_E_LIMIT, "N=%d needs %zu B of LDS in the slice sweep (max 163840)",
@@ -1489,10 +1496,10 @@ static int launch_sweep(dlsm_chain *h, IterRef iter, int algo, bool alloc_only =
         if (nsl <= 0) continue;
         if (h->model == DLSM_UNDIRECTED)
             hipLaunchKernelGGL((k_sweep_slice<DD, DLSM_UNDIRECTED>), dim3(nsl), dim3(SW_THREADS),
-                               lds, h->stream, v, iter, parity);
+                               lds, q, v, iter, parity);
         else
             hipLaunchKernelGGL((k_sweep_slice<DD, DLSM_DIRECTED>), dim3(nsl), dim3(SW_THREADS),
-                               lds, h->stream, v, iter, parity);
+                               lds, q, v, iter, parity);
     }
     HIPCHK(h, hipGetLastError());
     return DLSM_OK;
@@ -1515,15 +1522,13 @@ static int check_ready_sweep(dlsm_chain *h) {
     return DLSM_OK;
 }
 
-static int enqueue_sweep(dlsm_chain *h, IterRef iter, int algo, bool alloc_only = false) {
-    int rc = DLSM_OK;
-    if (!alloc_only) h->pipe_touched = false;
-    DISPATCH_D(h, h->D, rc = launch_sweep<DD>(h, iter, algo, alloc_only));
-    if (!alloc_only) {              // only a pipelined sweep leaves proposal buffers a tail can fill
-        if (!h->pipe_touched) h->next_prop_ok = false;
-        h->prop_drawn_for = -1;
-        if (h->sweep_part == 0) h->head_done_for = -1;
-    }
+// One sweep as `sc` describes it, and what it leaves for the next one on this handle (chain.hpp, SweepCarry)
+template <int DD>
+static int enqueue_sweep(dlsm_chain *h, SweepCall &sc, IterRef iter, int algo) {
+    const int rc = launch_sweep<DD>(h, sc, iter, algo);
+    if (sc.alloc_only) return rc;
+    if (!sc.left_proposals) h->carry.reset();           // only a pipelined sweep leaves proposal buffers a tail can fill
+    else if (!sc.head_only) h->carry.head_done_for = -1;    // (its head, enqueued ahead or not, is used up)
     return rc;
 }
 
@@ -1540,8 +1545,10 @@ int dlsm_sweep_positions(dlsm_chain *h, uint32_t iter, int algo) {
     int rc = check_sweep_algo(h, algo); if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     rc = check_ready_sweep(h); if (rc) return rc;
-    h->prop_drawn_for = -1;
-    rc = enqueue_sweep(h, IterRef{iter, nullptr}, algo); if (rc) return rc;
+    h->carry.reset();
+    SweepCall sc(Call{h->stream, read_knobs()});
+    DISPATCH_D(h, h->D, rc = enqueue_sweep<DD>(h, sc, IterRef{iter, nullptr}, algo));
+    if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return check_pipe_err(h);
 }
@@ -1583,12 +1590,7 @@ static int launch_post(dlsm_chain *h, const double *d_xref, int n_iter_procruste
 namespace {
 // The label block update's two launches.  LM_NODES nodes per workgroup on the f64 matrix cores when
 // the transition matrices and the nodes' tables fit in LDS together (config 3: 58 KB); the
-// wavefront-per-node kernel otherwise (DLSM_LABELS_KERNEL=wave forces it, for measurements).
-static bool labels_wave_forced() {
-    static const bool v = [] { const char *e = getenv("DLSM_LABELS_KERNEL"); return e && !strcmp(e, "wave"); }();
-    return v;
-}
-
+// wavefront-per-node kernel otherwise (DLSM_LABELS_KERNEL=wave forces it: labels_wave_forced).
 template <int KS>
 int launch_labels_mfma(dlsm_chain *h, const ChainView &v, uint32_t iter, hipStream_t q, int32_t *flag,
                        int32_t flag_val) {
@@ -1821,152 +1823,163 @@ int dlsm_trace_alloc(dlsm_chain *h, int n_total, double logp0) {
     return DLSM_OK;
 }
 
-// One Gibbs iteration of the undirected LSM on the handle's stream (lsm.py:474-572).
-// With `counter` the iteration index is read from device memory (captured graph: the
-// first kernel advances it), otherwise it is the value `it`.
-static int enqueue_lsm_iteration(dlsm_chain *h, int it, bool counter, int procrustes_ref,
-                                 bool alloc_only = false, bool draw_next = false) {
-    const size_t row = (size_t)h->T * h->N * h->D;
-    const IterRef ir{(uint32_t)it, counter ? &h->lsm->iter : nullptr};
-    int rc = DLSM_OK;
-    if (counter && !alloc_only)
-        hipLaunchKernelGGL(k_advance_iter, dim3(1), dim3(1), 0, h->stream, &h->lsm->iter);
-    const double *xref = procrustes_ref >= 0 ? h->trace_X + row * procrustes_ref : nullptr;
-    // undirected loop: the centring sums ride in the pipelined sweep's last launch when there is one
-    // (DLSM_POST_RIDE=0: a launch of their own); whether the rotation is on is decided here
-    h->post_ride_want = h->model == DLSM_UNDIRECTED && !counter && !alloc_only &&
-                        !(getenv("DLSM_POST_RIDE") && atoi(getenv("DLSM_POST_RIDE")) == 0);
-    h->post_ride_done = false;
-    if (h->post_ride_want) {
-        rc = ensure_partials(h, (size_t)ll_blocks(h) * 4 + (size_t)PS_BLOCKS * POST_W_MAX); if (rc) return rc;
-        const int nip = h->lsm_cfg.n_iter_procrustes;
-        h->post_ride_xref = (xref && (nip < 0 || it > nip)) ? xref : nullptr;
-    }
-    h->loop_draws_intercept = h->post_ride_want;     // the proposal pass also draws the intercept proposal
-    rc = enqueue_sweep(h, ir, h->lsm_cfg.sweep_algo, alloc_only);
-    h->post_ride_want = false; h->loop_draws_intercept = false;
-    if (rc) return rc;
-    const bool rode = h->post_ride_done;
-    h->post_ride_done = false;
-    if (rode && draw_next && h->next_prop_ok && h->next_prop.lsm_draw &&
-        !(getenv("DLSM_POST_FUSE") && atoi(getenv("DLSM_POST_FUSE")) == 0)) {
-        // The likelihood pass on the positions as the sweep left them (distances do not change under
-        // the centring pass's rotation and shift; its intercept proposal came with the sweep's
-        // proposals), then ONE launch for the rest of the iteration: centring, accept / reject, trace
-        // row, the next sweep's proposal pass (k_lsm_finalize_apply_propose).
-        int nrec_f = 0;
-        rc = loglik_records(h, 2, h->lsm->cand, nullptr, nullptr, &nrec_f); if (rc) return rc;
-        ProfScope ps(h, DLSM_K_FINALIZE);
-        ChainView v = h->view();
-        const PostFusedArgs pa{xref ? 1 : 0, h->lsm_cfg.n_iter_procrustes,
-                               h->partials + (size_t)ll_blocks(h) * 4, h->post_ride_nwg, h->post_ride_jl,
-                               h->post_ride_par, xref, h->trace_X};
-        DISPATCH_D(h, h->D, hipLaunchKernelGGL((k_lsm_finalize_apply_propose<DD>),
-                                               dim3(1 + propose_blocks(h->T, h->N)), dim3(256), 0, h->stream,
-                                               h->partials, nrec_f, h->lsm, h->intercept, h->trace_ic,
-                                               h->trace_logp, ir, v, h->next_prop, pa));
-        h->prop_drawn_for = (long)it + 1;
-        HIPCHK(h, hipGetLastError());
-        return DLSM_OK;
-    }
+}  // extern "C"
+
+// The directed models' steps behind the sweep (lsm.py:520-572, hdp_lpcm.py:855-874 with is_directed): centring,
+// intercept_in, intercept_out and the radii, around three likelihood passes (case-control: two).
+//   xref, n_iter_procrustes: the centring pass's Procrustes reference (NULL: none)
+//   ride_next: the last launch also draws the next sweep's proposals, when the sweep left buffers for them
+//   ll_in_logp_slot: the last launch leaves the network log-likelihood of the stored state in the row's
+//     log-posterior slot (the HDP-LPCM loop: the batched pass behind the run turns it into the log-posterior)
+// The sweep moved the positions, so the first step evaluates proposal and current state; after it the current
+// state's log-likelihood is carried (lsm->ll_cur) and the later steps evaluate their proposal only: 4 candidate
+// evaluations, not 6.  Launches besides the passes: 5, none of them the radii proposal's own.  The centring
+// launches draw the first intercept proposal, write the passes' gather records and carry the radii proposal's
+// gamma variates (pass 1) and its normalisation + density terms (pass 2: they file the proposal in the records'
+// second radius slot); the sum of a pass's records, the accept / reject and the next step's proposal share a
+// launch, the first of which carries the proposal's closing workgroup; the last pass's sum, the radii's
+// accept / reject and the trace row share the last launch.
+template <int DD>
+static int enqueue_directed_steps(dlsm_chain *h, const Call &c, IterRef ir, const double *xref, int n_iter_procrustes,
+                                  bool ride_next, int ll_in_logp_slot, bool alloc_only = false) {
     // case-control: the centring pass also writes the log-likelihood's gather records
     const bool pf = cc_prefetch_form(h);
-    if (pf) { DISPATCH_D(h, h->D, rc = ensure_xr<DD>(h)); if (rc) return rc; }
-    if (h->model == DLSM_UNDIRECTED) {
-        DISPATCH_D(h, h->D, rc = launch_post<DD>(h, xref, h->lsm_cfg.n_iter_procrustes, 1, h->lsm,
-                                                 ir, nullptr, alloc_only, h->trace_X, nullptr,
-                                                 rode ? h->post_ride_nwg : 0, h->post_ride_jl, h->post_ride_par));
-        if (rc) return rc;
-    }
-    if (alloc_only)     // (the directed loops' records: likelihood | centring | radii proposal)
-        return ensure_partials(h, (size_t)ll_blocks(h) * 4 + (size_t)PS_BLOCKS * POST_W_MAX +
-                                  (size_t)((h->N + DP_THREADS - 1) / DP_THREADS) * (1 + DP_COLS));
-    int nrec = 0;
-    if (h->model != DLSM_UNDIRECTED) {
-        // intercept_in, intercept_out, radii: propose -> fused two-candidate pass -> accept
-        ChainView v = h->view();
-        double *ll2 = h->dsmall + 16;
-        // The sweep moved the positions, so the first step evaluates proposal and current
-        // state; after it the current state's log-likelihood is carried (lsm->ll_cur) and the
-        // later steps evaluate their proposal only: 4 candidate evaluations, not 6.
-        // Launches besides the three passes: 5, none of them the radii proposal's own (round 2:
-        // eleven).  The centring launches draw the first intercept proposal, write the passes'
-        // gather records and carry the radii proposal's gamma variates (pass 1) and its
-        // normalisation + density terms (pass 2: they file the proposal in the records' second
-        // radius slot); the sum of a pass's records, the accept / reject and the next step's
-        // proposal share a launch, the first of which carries the proposal's closing workgroup;
-        // the last pass's sum, the radii's accept / reject and the trace row share the last
-        // launch, which can carry the next sweep's proposal pass.
-        const int nblk = (h->N + DP_THREADS - 1) / DP_THREADS;
-        constexpr int PW_MAX = POST_W_MAX;
-        const size_t n_post = (size_t)PS_BLOCKS * PW_MAX;
-        rc = ensure_partials(h, (size_t)ll_blocks(h) * 4 + n_post + (size_t)nblk * (1 + DP_COLS));
-        if (rc) return rc;
-        double *prec = h->partials + (size_t)ll_blocks(h) * 4;
-        double *rrec = prec + n_post, *rrec2 = rrec + nblk;
-        double *xr = pf ? h->xr : nullptr;
-        const long rows = (long)h->T * h->N;
-        const int nbp = (int)std::min<long>(PS_BLOCKS, (rows + PS2_THREADS - 1) / PS2_THREADS);
-        {
-            ProfScope psc(h, DLSM_K_CENTER);
-            const DirRider rg{1, nblk, h->radii, h->radii_alt, rrec, rrec2, xr};
-            DISPATCH_D(h, h->D, hipLaunchKernelGGL((k_post_reduce_dir<DD>), dim3(nbp + nblk), dim3(PS2_THREADS), 0,
-                                                   h->stream, v, xref, h->lsm_cfg.n_iter_procrustes, ir, prec,
-                                                   nbp, h->lsm, rg));
-            DISPATCH_D(h, h->D, hipLaunchKernelGGL((k_post_apply_dir<DD>), dim3(nbp + nblk), dim3(PS2_THREADS), 0,
-                                                   h->stream, v, xref ? 1 : 0, h->lsm_cfg.n_iter_procrustes, 1,
-                                                   prec, nbp, h->lsm, ir, h->trace_X, xr, nbp, rg));
-        }
-        ProfScope ps(h, DLSM_K_FINALIZE);
-        if (pf && !getenv("DLSM_CC_TWO_PASSES")) {
-            // case-control: both intercept steps behind ONE four-candidate pass (kernels_dirloop.hpp)
-            rc = loglik_records(h, 4, h->lsm->cand8, h->radii, h->radii, &nrec, true);
-            if (rc) return rc;
-            const DirRider rd{3, nblk, h->radii, h->radii_alt, rrec, rrec2, xr};
-            DISPATCH_D(h, h->D, hipLaunchKernelGGL((k_dir_reduce_accept_both<DD>), dim3(2), dim3(256), 0, h->stream,
-                                                   h->partials, nrec, ll2, v, h->lsm, h->intercept, ir, rd));
-        } else
-        for (int which = 0; which < 2; ++which) {
-            const int M = which == 0 ? 2 : 1;
-            rc = loglik_records(h, M, h->lsm->cand, h->radii, h->radii, &nrec, pf || which == 1);
-            if (rc) return rc;
-            const DirRider rd{which == 0 ? 3 : 0, nblk, h->radii, h->radii_alt, rrec, rrec2, xr};
-            DISPATCH_D(h, h->D, hipLaunchKernelGGL((k_dir_reduce_accept_intercept<DD>),
-                                                   dim3(1 + (which == 0 ? 1 : 0)), dim3(256), 0, h->stream,
-                                                   h->partials, nrec, M, ll2, v, h->lsm, h->intercept, which,
-                                                   which, which == 0 ? 1 : -1, ir, rd));
-        }
-        // the proposed radii at the current intercepts (one candidate)
-        rc = loglik_records(h, 1, h->intercept, h->radii_alt, h->radii_alt, &nrec, pf, 1);
-        if (rc) return rc;
-        const bool ride = draw_next && !counter && h->next_prop_ok;
-        const int grid = 1 + (ride ? (propose_blocks(h->T, h->N) + DR_THREADS / 256 - 1) / (DR_THREADS / 256) : 0);
-        DISPATCH_D(h, h->D, hipLaunchKernelGGL((k_dir_tail<DD>), dim3(grid), dim3(DR_THREADS), 0, h->stream,
-                                               h->partials, nrec, ll2, v, h->lsm, h->radii, h->radii_alt,
-                                               h->intercept, h->trace_ic, h->trace_radii, h->trace_logp,
-                                               ir, h->next_prop, ride ? 1 : 0));
-        if (ride) h->prop_drawn_for = (long)it + 1;
-        HIPCHK(h, hipGetLastError());
-        return DLSM_OK;
-    }
-    rc = loglik_records(h, 2, h->lsm->cand, nullptr, nullptr, &nrec); if (rc) return rc;
+    int rc = DLSM_OK;
+    if (pf) { rc = ensure_xr<DD>(h); if (rc) return rc; }
+    // the records: likelihood | centring | radii proposal
+    const int nblk = (h->N + DP_THREADS - 1) / DP_THREADS;
+    const size_t n_post = (size_t)PS_BLOCKS * POST_W_MAX;
+    rc = ensure_partials(h, (size_t)ll_blocks(h) * 4 + n_post + (size_t)nblk * (1 + DP_COLS));
+    if (rc || alloc_only) return rc;
+    ChainView v = h->view();
+    double *ll2 = h->dsmall + 16;
+    double *prec = h->partials + (size_t)ll_blocks(h) * 4;
+    double *rrec = prec + n_post, *rrec2 = rrec + nblk;
+    double *xr = pf ? h->xr : nullptr;
+    const long rows = (long)h->T * h->N;
+    const int nbp = (int)std::min<long>(PS_BLOCKS, (rows + PS2_THREADS - 1) / PS2_THREADS);
     {
-        ProfScope ps(h, DLSM_K_FINALIZE);
-        if (draw_next && !counter && h->next_prop_ok) {
-            // the next sweep's proposal pass rides along (kernels_tail_propose.hpp)
-            ChainView v = h->view();
-            DISPATCH_D(h, h->D, hipLaunchKernelGGL((k_lsm_finalize_propose<DD>),
-                                                   dim3(1 + propose_blocks(h->T, h->N)), dim3(256), 0,
-                                                   h->stream, h->partials, nrec, h->lsm, h->intercept,
-                                                   h->trace_ic, h->trace_logp, ir, v, h->next_prop));
-            h->prop_drawn_for = (long)it + 1;
-        } else
-            hipLaunchKernelGGL(k_lsm_finalize, dim3(1), dim3(256), 0, h->stream, h->partials, nrec,
-                               h->lsm, h->intercept, h->trace_ic, h->trace_logp, ir);
+        ProfScope psc(h, DLSM_K_CENTER);
+        const DirRider rg{1, nblk, h->radii, h->radii_alt, rrec, rrec2, xr};
+        hipLaunchKernelGGL((k_post_reduce_dir<DD>), dim3(nbp + nblk), dim3(PS2_THREADS), 0, h->stream, v, xref,
+                           n_iter_procrustes, ir, prec, nbp, h->lsm, rg);
+        hipLaunchKernelGGL((k_post_apply_dir<DD>), dim3(nbp + nblk), dim3(PS2_THREADS), 0, h->stream, v,
+                           xref ? 1 : 0, n_iter_procrustes, 1, prec, nbp, h->lsm, ir, h->trace_X, xr, nbp, rg);
     }
+    ProfScope ps(h, DLSM_K_FINALIZE);
+    int nrec = 0;
+    if (pf) {
+        // case-control: both intercept steps behind ONE four-candidate pass (kernels_dirloop.hpp)
+        rc = launch_loglik_records<DD>(h, c, false, 4, h->lsm->cand8, h->radii, h->radii, &nrec, true);
+        if (rc) return rc;
+        const DirRider rd{3, nblk, h->radii, h->radii_alt, rrec, rrec2, xr};
+        hipLaunchKernelGGL((k_dir_reduce_accept_both<DD>), dim3(2), dim3(256), 0, h->stream, h->partials, nrec,
+                           ll2, v, h->lsm, h->intercept, ir, rd);
+    } else
+    for (int which = 0; which < 2; ++which) {
+        const int M = which == 0 ? 2 : 1;
+        rc = launch_loglik_records<DD>(h, c, false, M, h->lsm->cand, h->radii, h->radii, &nrec, which == 1);
+        if (rc) return rc;
+        const DirRider rd{which == 0 ? 3 : 0, nblk, h->radii, h->radii_alt, rrec, rrec2, xr};
+        hipLaunchKernelGGL((k_dir_reduce_accept_intercept<DD>), dim3(1 + (which == 0 ? 1 : 0)), dim3(256), 0,
+                           h->stream, h->partials, nrec, M, ll2, v, h->lsm, h->intercept, which, which,
+                           which == 0 ? 1 : -1, ir, rd);
+    }
+    // the proposed radii at the current intercepts (one candidate)
+    rc = launch_loglik_records<DD>(h, c, false, 1, h->intercept, h->radii_alt, h->radii_alt, &nrec, pf, 1);
+    if (rc) return rc;
+    const bool ride = ride_next && h->carry.next_prop_ok;
+    const int grid = 1 + (ride ? (propose_blocks(h->T, h->N) + DR_THREADS / 256 - 1) / (DR_THREADS / 256) : 0);
+    hipLaunchKernelGGL((k_dir_tail<DD>), dim3(grid), dim3(DR_THREADS), 0, h->stream, h->partials, nrec, ll2, v,
+                       h->lsm, h->radii, h->radii_alt, h->intercept, h->trace_ic, h->trace_radii, h->trace_logp,
+                       ir, h->carry.next_prop, ride ? 1 : 0, ll_in_logp_slot);
+    if (ride) h->carry.prop_drawn_for = (long)ir.value + 1;
     HIPCHK(h, hipGetLastError());
     return DLSM_OK;
 }
+
+// The undirected LSM's steps behind a sweep whose last launch carried the centring sums, when the next sweep's
+// proposals can be drawn ahead: the likelihood pass on the positions as the sweep left them (distances do not
+// change under the centring pass's rotation and shift; its intercept proposal came with the sweep's proposals),
+// then ONE launch for the rest of the iteration: centring, accept / reject, trace row, the next sweep's
+// proposal pass (k_lsm_finalize_apply_propose).
+template <int DD>
+static int enqueue_lsm_fused_finalize(dlsm_chain *h, const Call &c, IterRef ir, const double *xref,
+                                      const SweepCall &sc) {
+    int nrec = 0;
+    int rc = launch_loglik_records<DD>(h, c, false, 2, h->lsm->cand, nullptr, nullptr, &nrec); if (rc) return rc;
+    ProfScope ps(h, DLSM_K_FINALIZE);
+    ChainView v = h->view();
+    const PostFusedArgs pa{xref ? 1 : 0, h->lsm_cfg.n_iter_procrustes, h->partials + (size_t)ll_blocks(h) * 4,
+                           sc.nwg, sc.jl, sc.par, xref, h->trace_X};
+    hipLaunchKernelGGL((k_lsm_finalize_apply_propose<DD>), dim3(1 + propose_blocks(h->T, h->N)), dim3(256), 0,
+                       h->stream, h->partials, nrec, h->lsm, h->intercept, h->trace_ic, h->trace_logp, ir, v,
+                       h->carry.next_prop, pa);
+    h->carry.prop_drawn_for = (long)ir.value + 1;
+    HIPCHK(h, hipGetLastError());
+    return DLSM_OK;
+}
+
+// ... and otherwise: the centring pass (its sums from the sweep's last launch when they rode there), the
+// likelihood pass, the intercept's accept / reject with the trace row - and, with ride_next, the next sweep's
+// proposal pass in that launch (kernels_tail_propose.hpp)
+template <int DD>
+static int enqueue_lsm_plain_finalize(dlsm_chain *h, const Call &c, IterRef ir, const double *xref,
+                                      const SweepCall &sc, bool ride_next) {
+    int rc = launch_post<DD>(h, xref, h->lsm_cfg.n_iter_procrustes, 1, h->lsm, ir, nullptr, sc.alloc_only,
+                             h->trace_X, nullptr, sc.rode ? sc.nwg : 0, sc.jl, sc.par);
+    if (rc) return rc;
+    if (sc.alloc_only)      // (sized for the directed loops' records too: likelihood | centring | radii proposal)
+        return ensure_partials(h, (size_t)ll_blocks(h) * 4 + (size_t)PS_BLOCKS * POST_W_MAX +
+                                  (size_t)((h->N + DP_THREADS - 1) / DP_THREADS) * (1 + DP_COLS));
+    int nrec = 0;
+    rc = launch_loglik_records<DD>(h, c, false, 2, h->lsm->cand, nullptr, nullptr, &nrec); if (rc) return rc;
+    ProfScope ps(h, DLSM_K_FINALIZE);
+    if (ride_next && h->carry.next_prop_ok) {
+        ChainView v = h->view();
+        hipLaunchKernelGGL((k_lsm_finalize_propose<DD>), dim3(1 + propose_blocks(h->T, h->N)), dim3(256), 0,
+                           h->stream, h->partials, nrec, h->lsm, h->intercept, h->trace_ic, h->trace_logp, ir, v,
+                           h->carry.next_prop);
+        h->carry.prop_drawn_for = (long)ir.value + 1;
+    } else
+        hipLaunchKernelGGL(k_lsm_finalize, dim3(1), dim3(256), 0, h->stream, h->partials, nrec, h->lsm,
+                           h->intercept, h->trace_ic, h->trace_logp, ir);
+    HIPCHK(h, hipGetLastError());
+    return DLSM_OK;
+}
+
+// One Gibbs iteration of the LSM loops on the chain's queue (lsm.py:474-572).  With `counter` the iteration
+// index is read from device memory (captured graph: the first kernel advances it), otherwise it is the value
+// `it`.  draw_next: another iteration follows, and its sweep's proposals may be drawn by this one's last launch.
+template <int DD>
+static int enqueue_lsm_iteration(dlsm_chain *h, const Call &c, int it, bool counter, int procrustes_ref,
+                                 bool alloc_only = false, bool draw_next = false) {
+    const size_t row = (size_t)h->T * h->N * h->D;
+    const IterRef ir{(uint32_t)it, counter ? &h->lsm->iter : nullptr};
+    const int nip = h->lsm_cfg.n_iter_procrustes;
+    if (counter && !alloc_only)
+        hipLaunchKernelGGL(k_advance_iter, dim3(1), dim3(1), 0, h->stream, &h->lsm->iter);
+    const double *xref = procrustes_ref >= 0 ? h->trace_X + row * procrustes_ref : nullptr;
+    SweepCall sc(c);
+    sc.alloc_only = alloc_only;
+    // undirected loop: the centring sums ride in the pipelined sweep's last launch when there is one
+    // (DLSM_POST_RIDE=0: a launch of their own); whether the rotation is on is decided here
+    sc.want_post_ride = h->model == DLSM_UNDIRECTED && !counter && !alloc_only && c.knobs.post_ride;
+    if (sc.want_post_ride) {
+        int rc = ensure_partials(h, (size_t)ll_blocks(h) * 4 + (size_t)PS_BLOCKS * POST_W_MAX); if (rc) return rc;
+        sc.xref = (xref && (nip < 0 || it > nip)) ? xref : nullptr;
+    }
+    sc.draw_intercept = sc.want_post_ride;      // the proposal pass also draws the intercept proposal
+    int rc = enqueue_sweep<DD>(h, sc, ir, h->lsm_cfg.sweep_algo); if (rc) return rc;
+    const bool ride_next = draw_next && !counter;
+    if (h->model != DLSM_UNDIRECTED)
+        return enqueue_directed_steps<DD>(h, c, ir, xref, nip, ride_next, 0, alloc_only);
+    if (sc.rode && draw_next && h->carry.next_prop_ok && h->carry.next_prop.lsm_draw && c.knobs.post_fuse)
+        return enqueue_lsm_fused_finalize<DD>(h, c, ir, xref, sc);
+    return enqueue_lsm_plain_finalize<DD>(h, c, ir, xref, sc, ride_next);
+}
+
+extern "C" {
 
 int dlsm_lsm_run(dlsm_chain *h, int first, int count, int procrustes_ref) {
     NEED(h, h != nullptr, "null handle");
@@ -1983,19 +1996,19 @@ int dlsm_lsm_run(dlsm_chain *h, int first, int count, int procrustes_ref) {
     // frozen in a graph, hence the device-side iteration counter.  On MI355X the GPU is
     // the limit either way (eager 1874 it/s, replay 1840 it/s at C2), so eager is the
     // default; replay is for hosts that cannot spare a core per chain.
+    const Call call{h->stream, read_knobs()};
     const bool want_graph = h->model == DLSM_UNDIRECTED && !h->profiling && !h->graph_failed &&
-                            count >= 2 &&
-                            getenv("DLSM_GRAPH") && atoi(getenv("DLSM_GRAPH")) == 1;
+                            count >= 2 && call.knobs.graph;
     if (want_graph) {
         if (!h->graph_exec || h->graph_ref != procrustes_ref ||
             h->graph_algo != h->lsm_cfg.sweep_algo) {
             drop_graph(h);
-            rc = enqueue_lsm_iteration(h, first, true, procrustes_ref, true);   // allocations
+            DISPATCH_D(h, h->D, rc = enqueue_lsm_iteration<DD>(h, call, first, true, procrustes_ref, true));  // allocations
             if (rc) return rc;
             HIPCHK(h, hipStreamSynchronize(h->stream));
             bool ok = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
             if (ok) {
-                rc = enqueue_lsm_iteration(h, first, true, procrustes_ref);
+                DISPATCH_D(h, h->D, rc = enqueue_lsm_iteration<DD>(h, call, first, true, procrustes_ref));
                 hipError_t e = hipStreamEndCapture(h->stream, &h->graph);
                 ok = rc == DLSM_OK && e == hipSuccess && h->graph &&
                      hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0) == hipSuccess;
@@ -2019,17 +2032,14 @@ int dlsm_lsm_run(dlsm_chain *h, int first, int count, int procrustes_ref) {
             return DLSM_OK;
         }
     }
-    // (read per call: the tests switch it inside one process)
-    const bool ride = !(getenv("DLSM_TAIL_PROPOSE") && atoi(getenv("DLSM_TAIL_PROPOSE")) == 0);
-    h->prop_drawn_for = -1;
-    for (int it = first; it < first + count; ++it) {
-        rc = enqueue_lsm_iteration(h, it, false,
-                                   it > h->lsm_cfg.n_iter_procrustes ? procrustes_ref : -1, false,
-                                   ride && it + 1 < first + count);
-        if (rc) return rc;
-    }
-    h->prop_drawn_for = -1;
-    return DLSM_OK;
+    h->carry.reset();
+    DISPATCH_D(h, h->D, {
+        for (int it = first; it < first + count && !rc; ++it)
+            rc = enqueue_lsm_iteration<DD>(h, call, it, false, it > h->lsm_cfg.n_iter_procrustes ? procrustes_ref : -1,
+                                           false, call.knobs.tail_propose && it + 1 < first + count);
+    });
+    h->carry.reset();
+    return rc;
 }
 
 int dlsm_trace_read(dlsm_chain *h, int first, int count, double *Xs, double *intercepts,

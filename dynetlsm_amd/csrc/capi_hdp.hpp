@@ -38,12 +38,6 @@ void hdp_free_trace(dlsm_chain *h) {
     h->htr_z = nullptr; h->htr_n = 0; h->htr_K = 0;
 }
 
-// polls of ~1 us of the waits INSIDE kernels (kernels_hdploop.hpp, HdpFork); DLSM_HDP_FORK_BUDGET overrides it
-static int hdp_fork_budget() {
-    const char *e = getenv("DLSM_HDP_FORK_BUDGET");
-    return e ? atoi(e) : (1 << 22);
-}
-
 // "queue `s` goes on when flags[which] has reached the ticket": a wait of the QUEUE itself
 // (hipStreamWaitValue32: the command processor polls the word, no wavefront does and no budget runs out -
 // round-4 advice: a gate kernel enqueued while the chain's queue still held seconds of earlier work used up
@@ -60,81 +54,26 @@ static int hdp_queue_wait(dlsm_chain *h, hipStream_t s, const HdpFork &fk, int w
 }
 
 template <int DD>
-int enqueue_hdp_iteration(dlsm_chain *h, int it, bool draw_next) {
+int enqueue_hdp_iteration(dlsm_chain *h, const Call &c, int it, bool draw_next) {
     const IterRef ir{(uint32_t)it, nullptr};
     const int T = h->T, K = h->K, N = h->N;
-    // (the centring sums ride in the pipelined sweep's last launch when there is one)
-    h->post_ride_want = h->model == DLSM_UNDIRECTED &&
-                        !(getenv("DLSM_POST_RIDE") && atoi(getenv("DLSM_POST_RIDE")) == 0);
-    h->post_ride_done = false; h->post_ride_xref = nullptr;
-    int rc = DLSM_OK;
-    if (h->post_ride_want) { rc = ensure_partials(h, (size_t)ll_blocks(h) * 4 + (size_t)PS_BLOCKS * POST_W_MAX); if (rc) return rc; }
-    rc = enqueue_sweep(h, ir, h->hdp_cfg.sweep_algo);
-    h->post_ride_want = false;
-    if (rc) return rc;
-    const bool rode = h->post_ride_done;
-    h->post_ride_done = false;
     const bool directed = h->model != DLSM_UNDIRECTED;
-    if (directed) {
-        // hdp_lpcm.py:855-874 with is_directed: centring, intercept_in, intercept_out and the radii
-        // step around three likelihood passes - the launches of dlsm_lsm_run's directed loop
-        // (enqueue_lsm_iteration, kernels_dirloop.hpp), without a Procrustes reference and with the
-        // last launch leaving the network log-likelihood of the stored state in the row's
-        // log-posterior slot (the batched pass behind the run turns it into the log-posterior)
-        const bool pf = cc_prefetch_form(h);
-        if (pf) { rc = ensure_xr<DD>(h); if (rc) return rc; }
-        ChainView vd = h->view();
-        double *ll2 = h->dsmall + 16;
-        const int nblk = (h->N + DP_THREADS - 1) / DP_THREADS;
-        constexpr int PW_MAX = POST_W_MAX;
-        const size_t n_post = (size_t)PS_BLOCKS * PW_MAX;
-        rc = ensure_partials(h, (size_t)ll_blocks(h) * 4 + n_post + (size_t)nblk * (1 + DP_COLS));
-        if (rc) return rc;
-        double *prec = h->partials + (size_t)ll_blocks(h) * 4;
-        double *rrec = prec + n_post, *rrec2 = rrec + nblk;
-        double *xr = pf ? h->xr : nullptr;
-        const long rows = (long)h->T * h->N;
-        const int nbp = (int)std::min<long>(PS_BLOCKS, (rows + PS2_THREADS - 1) / PS2_THREADS);
-        {
-            ProfScope psc(h, DLSM_K_CENTER);
-            const DirRider rg{1, nblk, h->radii, h->radii_alt, rrec, rrec2, xr};
-            hipLaunchKernelGGL((k_post_reduce_dir<DD>), dim3(nbp + nblk), dim3(PS2_THREADS), 0, h->stream, vd,
-                               (const double *)nullptr, 0, ir, prec, nbp, h->lsm, rg);
-            hipLaunchKernelGGL((k_post_apply_dir<DD>), dim3(nbp + nblk), dim3(PS2_THREADS), 0, h->stream, vd, 0, 0,
-                               1, prec, nbp, h->lsm, ir, h->trace_X, xr, nbp, rg);
-        }
-        {
-            ProfScope psf(h, DLSM_K_FINALIZE);
-            int nrec_d = 0;
-            if (pf && !getenv("DLSM_CC_TWO_PASSES")) {      // (as the directed LSM loop: capi.hip)
-                rc = loglik_records(h, 4, h->lsm->cand8, h->radii, h->radii, &nrec_d, true);
-                if (rc) return rc;
-                const DirRider rd{3, nblk, h->radii, h->radii_alt, rrec, rrec2, xr};
-                hipLaunchKernelGGL((k_dir_reduce_accept_both<DD>), dim3(2), dim3(256), 0, h->stream, h->partials,
-                                   nrec_d, ll2, vd, h->lsm, h->intercept, ir, rd);
-            } else
-            for (int which = 0; which < 2; ++which) {
-                const int M = which == 0 ? 2 : 1;
-                rc = loglik_records(h, M, h->lsm->cand, h->radii, h->radii, &nrec_d, pf || which == 1);
-                if (rc) return rc;
-                const DirRider rd{which == 0 ? 3 : 0, nblk, h->radii, h->radii_alt, rrec, rrec2, xr};
-                hipLaunchKernelGGL((k_dir_reduce_accept_intercept<DD>), dim3(1 + (which == 0 ? 1 : 0)), dim3(256), 0,
-                                   h->stream, h->partials, nrec_d, M, ll2, vd, h->lsm, h->intercept, which, which,
-                                   which == 0 ? 1 : -1, ir, rd);
-            }
-            rc = loglik_records(h, 1, h->intercept, h->radii_alt, h->radii_alt, &nrec_d, pf, 1);
-            if (rc) return rc;
-            hipLaunchKernelGGL((k_dir_tail<DD>), dim3(1), dim3(DR_THREADS), 0, h->stream, h->partials, nrec_d, ll2,
-                               vd, h->lsm, h->radii, h->radii_alt, h->intercept, h->trace_ic, h->trace_radii,
-                               h->trace_logp, ir, h->next_prop, 0, 1);
-        }
-        HIPCHK(h, hipGetLastError());
-    } else {
-    // centring; workgroup 0 draws the intercept proposal; the positions' trace row
-    rc = launch_post<DD>(h, nullptr, 0, 1, h->lsm, ir, nullptr, false, h->trace_X, nullptr,
-                         rode ? h->post_ride_nwg : 0, h->post_ride_jl, h->post_ride_par);
+    int rc = DLSM_OK;
+    SweepCall sc(c);
+    // (the centring sums ride in the pipelined sweep's last launch when there is one)
+    sc.want_post_ride = !directed && c.knobs.post_ride;
+    if (sc.want_post_ride) { rc = ensure_partials(h, (size_t)ll_blocks(h) * 4 + (size_t)PS_BLOCKS * POST_W_MAX); if (rc) return rc; }
+    rc = enqueue_sweep<DD>(h, sc, ir, h->hdp_cfg.sweep_algo);
     if (rc) return rc;
-    }
+    if (directed)
+        // hdp_lpcm.py:855-874 with is_directed - the launches of dlsm_lsm_run's directed loop, without a
+        // Procrustes reference and with the network log-likelihood left in the row's log-posterior slot
+        rc = enqueue_directed_steps<DD>(h, c, ir, nullptr, 0, false, 1);
+    else
+        // centring; workgroup 0 draws the intercept proposal; the positions' trace row
+        rc = launch_post<DD>(h, nullptr, 0, 1, h->lsm, ir, nullptr, false, h->trace_X, nullptr,
+                             sc.rode ? sc.nwg : 0, sc.jl, sc.par);
+    if (rc) return rc;
     // The label block update needs the centred positions and last iteration's mixture, not the
     // intercept's likelihood records (31 us at config 3), and those do not need the labels: with
     // `fork` the pass and the intercept step go to a queue of their own beside the label update and
@@ -144,7 +83,8 @@ int enqueue_hdp_iteration(dlsm_chain *h, int it, bool draw_next) {
     ChainView v = h->view();
     HdpLoopBuf hb = hdp_loop_buf(h);
     HdpFork fk{nullptr, 0, 0, nullptr};
-    if (fork) fk = HdpFork{h->fork_flags, ++h->fork_ticket, hdp_fork_budget(), h->fork_err_dev};
+    // (budget: polls of ~1 us of the waits INSIDE kernels - kernels_hdploop.hpp, HdpFork; DLSM_HDP_FORK_BUDGET)
+    if (fork) fk = HdpFork{h->fork_flags, ++h->fork_ticket, c.knobs.hdp_fork_budget, h->fork_err_dev};
     {   // label block update (sample_labels.py:134-190) with the transition matrices on the device
         ProfScope ps(h, DLSM_K_LABELS);
         rc = launch_sample_labels<DD>(h, v, (uint32_t)it, nullptr, h->stream,
@@ -155,36 +95,35 @@ int enqueue_hdp_iteration(dlsm_chain *h, int it, bool draw_next) {
     bool head = false;
     if (fork) {
         rc = hdp_queue_wait(h, h->fork_stream, fk, (int)HF_CENTRED); if (rc) return rc;
-        hipStream_t keep = h->stream;
-        h->stream = h->fork_stream; h->ll_beside_chain = true;
-        rc = loglik_records(h, 2, h->lsm->cand, nullptr, nullptr, &nrec);
-        h->stream = keep; h->ll_beside_chain = false;
-        if (rc) return rc;
+        const Call side{h->fork_stream, c.knobs};
+        rc = launch_loglik_records<DD>(h, side, true, 2, h->lsm->cand, nullptr, nullptr, &nrec); if (rc) return rc;
         // ... and, when another iteration follows and its sweep is the pipelined one, the HEAD of that sweep:
         // the proposal pass and the first, evaluate-only launch need the settled intercept, the positions and
         // the step sizes - nothing the label update or the conjugate draws produce - so they run here, beside
         // those, and the chain's queue starts the sweep at its second launch.  The flag then says "head done".
-        head = draw_next && h->next_prop_ok && resolve_sweep_algo(h, h->hdp_cfg.sweep_algo) == 4 &&
-               !(getenv("DLSM_HDP_HEAD") && atoi(getenv("DLSM_HDP_HEAD")) == 0);
+        head = draw_next && h->carry.next_prop_ok && resolve_sweep_algo(h, h->hdp_cfg.sweep_algo) == 4 &&
+               c.knobs.hdp_head;
         if (head)       // (the intercept step and the proposal pass in one launch)
             hipLaunchKernelGGL((k_hdp_intercept_fork_propose<DD>), dim3(1 + propose_blocks(T, N)), dim3(256), 0,
                                h->fork_stream, h->partials, nrec, h->lsm, h->hdp, h->intercept, h->trace_ic, it,
-                               v, h->next_prop);
+                               v, h->carry.next_prop);
         else
         hipLaunchKernelGGL(k_hdp_intercept_fork, dim3(1), dim3(HDP_THREADS), 0, h->fork_stream, h->partials, nrec,
                            h->lsm, h->hdp, h->intercept, h->trace_ic, it, fk, (int)HF_SETTLED);
         if (head) {
-            h->prop_drawn_for = (long)it + 1;      // (the sweep's head below finds its proposals drawn)
-            h->stream = h->fork_stream; h->sweep_part = 1;
-            rc = enqueue_sweep(h, IterRef{(uint32_t)(it + 1), nullptr}, h->hdp_cfg.sweep_algo);
-            h->sweep_part = 0; h->stream = keep;
+            h->carry.prop_drawn_for = (long)it + 1;      // (the sweep's head below finds its proposals drawn)
+            SweepCall hs(side);
+            hs.head_only = true;
+            rc = enqueue_sweep<DD>(h, hs, IterRef{(uint32_t)(it + 1), nullptr}, h->hdp_cfg.sweep_algo);
             if (rc) return rc;
             // ("head done" as a write packet of the queue - hipStreamWriteValue32 - instead of this one-wavefront
             // launch: 3980 against 4008 it/s, round 5)
             hipLaunchKernelGGL(k_fork_set, dim3(1), dim3(64), 0, h->fork_stream, fk, (int)HF_SETTLED);
-            h->prop_drawn_for = (long)it + 1; h->head_done_for = (long)it + 1;
+            h->carry.prop_drawn_for = (long)it + 1; h->carry.head_done_for = (long)it + 1;
         }
-    } else if (!directed) { rc = loglik_records(h, 2, h->lsm->cand, nullptr, nullptr, &nrec); if (rc) return rc; }
+    } else if (!directed) {
+        rc = launch_loglik_records<DD>(h, c, false, 2, h->lsm->cand, nullptr, nullptr, &nrec); if (rc) return rc;
+    }
     ProfScope ps(h, DLSM_K_HDP_TAIL);
     const int n_tab = T * hdp_tab_groups(K);    // (the label counts are a role of this launch)
     // (directed models: the intercepts were settled above - the launch goes without the role's workgroup)
@@ -198,14 +137,14 @@ int enqueue_hdp_iteration(dlsm_chain *h, int it, bool draw_next) {
     HdpTrace tr{h->trace_ic, h->trace_logp, h->htr_mu, h->htr_sigma, h->htr_beta, h->htr_w,
                 h->htr_lambda, h->htr_hyper};
     if (head) {                             // the sweep's head is on the second queue: this launch waits for it
-        ProposeBuf none = h->next_prop;
+        ProposeBuf none = h->carry.next_prop;
         none.consts = nullptr;
         hipLaunchKernelGGL((k_hdp_hypers_propose<DD>), dim3(1), dim3(HH_THREADS), 0, h->stream, v, hb, h->hdp, tr,
                            ir, none, fk);
-    } else if (draw_next && h->next_prop_ok) {     // with the next sweep's proposal pass (kernels_tail_propose.hpp)
+    } else if (draw_next && h->carry.next_prop_ok) {     // with the next sweep's proposal pass (kernels_tail_propose.hpp)
         hipLaunchKernelGGL((k_hdp_hypers_propose<DD>), dim3(1 + propose_blocks(T, N)), dim3(HH_THREADS), 0,
-                           h->stream, v, hb, h->hdp, tr, ir, h->next_prop, fk);
-        h->prop_drawn_for = (long)it + 1;
+                           h->stream, v, hb, h->hdp, tr, ir, h->carry.next_prop, fk);
+        h->carry.prop_drawn_for = (long)it + 1;
     } else {
         hipLaunchKernelGGL(k_hdp_hypers, dim3(1), dim3(HH_THREADS), 0, h->stream, v, hb, h->hdp, tr, ir);
         // whatever follows on the chain's queue (a sweep with its own proposal pass) starts from the
@@ -244,29 +183,20 @@ int enqueue_hdp_logp_batch(dlsm_chain *h, int first, int count) {
 // The likelihood pass on a queue of its own: the undirected model with the matrix-core label kernel
 // (which carries the hand-over flag), outside profiling runs (their per-launch events serialise the
 // queues).  DLSM_HDP_QUEUES=1 never, =2 always; otherwise only while this is the process's only live
-// chain.  Every waiter is ENQUEUED after the launch it waits for, so even two queues that the runtime
+// chain (alone_or_forced).  Every waiter is ENQUEUED after the launch it waits for, so even two queues that the runtime
 // has mapped onto one hardware queue (more streams alive than it has queues) cannot wait for each
 // other for ever - they only lose the overlap; the poll budget is the net under that argument.  The
 // rule is about what was measured: one chain alone on its device gains, chains that share a device
 // (threads of one process: untested; processes: 2.4 times slower, multichain.launch_ranks) do not.
-int hdp_fork_arm(dlsm_chain *h) {
-    const char *e = getenv("DLSM_HDP_QUEUES");
-    const int mode = e ? atoi(e) : 0;
+int hdp_fork_arm(dlsm_chain *h, const Knobs &kn) {
     h->fork_armed = false;
-    if (mode == 1 || h->model != DLSM_UNDIRECTED || h->profiling || !labels_mfma_path(h)) return DLSM_OK;
-    if (mode != 2 && g_live_chains.load() != 1) return DLSM_OK;
+    if (!alone_or_forced(kn.hdp_queues, 1, 2) || h->model != DLSM_UNDIRECTED || h->profiling || !labels_mfma_path(h))
+        return DLSM_OK;
     if (!h->fork_stream) {
         int lo = 0, hi = 0;                        // (numerically greatest = lowest priority: the pass
         HIPCHK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));   // yields to the chain's small launches)
         // (measured, profiles/r04_hdp_two_queues.md: the priority changes nothing; capping the pass's
         // workgroups per CU with unused LDS changes nothing; a CU mask of 160 is +0.5 %, 192 .. 240 are -1 %)
-        const char *ec = getenv("DLSM_HDP_FORK_CUS");
-        if (ec && atoi(ec) > 0) {                  // (experiment: the pass on a subset of the CUs)
-            const int ncu = atoi(ec);
-            uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int i = 0; i < ncu && i < 256; ++i) mask[i >> 5] |= 1u << (i & 31);
-            HIPCHK(h, hipExtStreamCreateWithCUMask(&h->fork_stream, 8, mask));
-        } else
         HIPCHK(h, hipStreamCreateWithPriority(&h->fork_stream, hipStreamNonBlocking, lo));
         HIPCHK(h, hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
         HIPCHK(h, hipMalloc((void **)&h->fork_flags, 64));
@@ -275,15 +205,12 @@ int hdp_fork_arm(dlsm_chain *h) {
         int can = 0;
         if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, h->device) != hipSuccess) can = 0;
         (void)hipGetLastError();
-        const char *eg = getenv("DLSM_HDP_GATE");
         // (under rocprofv3's counter collection - it serialises the dispatches of all queues - the queue-level
         // wait never returned: a process the profiler's tool library is loaded into keeps the gate kernel)
-        const bool profiler = getenv("ROCP_TOOL_LIBRARIES") != nullptr || getenv("ROCPROFILER_REGISTER_FORCE_LOAD") != nullptr;
-        h->fork_wait_value = can != 0 && !profiler && !(eg && strcmp(eg, "kernel") == 0);
+        h->fork_wait_value = can != 0 && !kn.profiler && !kn.hdp_gate_kernel;
         h->fork_ticket = 0;
     }
     h->fork_armed = true;
-    if (getenv("DLSM_DEBUG")) fprintf(stderr, "dlsm: HDP-LPCM loop on two queues (live chains %d)\n", g_live_chains.load());
     return DLSM_OK;
 }
 
@@ -362,7 +289,10 @@ int dlsm_hdp_configure(dlsm_chain *h, const dlsm_hdp_config *cfg, const double *
     rc = h2d(h, hb.beta, beta, (size_t)K); if (rc) return rc;
     rc = h2d(h, h->lab_w, weights, (size_t)T * K * K); if (rc) return rc;
     // allocations of the sweep / post / log-likelihood launchers (so that the run only enqueues)
-    rc = enqueue_sweep(h, IterRef{0, nullptr}, cfg->sweep_algo, true); if (rc) return rc;
+    SweepCall sizing(Call{h->stream, read_knobs()});
+    sizing.alloc_only = true;
+    DISPATCH_D(h, h->D, rc = enqueue_sweep<DD>(h, sizing, IterRef{0, nullptr}, cfg->sweep_algo));
+    if (rc) return rc;
     if (h->model == DLSM_UNDIRECTED) {
         DISPATCH_D(h, h->D, rc = launch_post<DD>(h, nullptr, 0, 1, h->lsm, IterRef{0, nullptr}, nullptr, true));
         if (rc) return rc;
@@ -445,21 +375,19 @@ int dlsm_hdp_run(dlsm_chain *h, int first, int count) {
          "iteration range out of the trace");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = check_ready_hdp(h); if (rc) return rc;
-    // (read per call: the tests switch it inside one process)
-    const bool ride = !(getenv("DLSM_TAIL_PROPOSE") && atoi(getenv("DLSM_TAIL_PROPOSE")) == 0);
-    h->prop_drawn_for = -1; h->head_done_for = -1;
-    rc = hdp_fork_arm(h); if (rc) return rc;
-    for (int it = first; it < first + count; ++it) {
-        DISPATCH_D(h, h->D, rc = enqueue_hdp_iteration<DD>(h, it, ride && it + 1 < first + count));
-        if (rc) break;
-    }
+    const Call call{h->stream, read_knobs()};
+    h->carry.reset();
+    rc = hdp_fork_arm(h, call.knobs); if (rc) return rc;
+    DISPATCH_D(h, h->D, {
+        for (int it = first; it < first + count && !rc; ++it)
+            rc = enqueue_hdp_iteration<DD>(h, call, it, call.knobs.tail_propose && it + 1 < first + count);
+    });
     if (h->fork_armed && count > 0) {       // ONE event per call: the second queue's last intercept step
         HIPCHK(h, hipEventRecord(h->fork_ev, h->fork_stream));
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->fork_ev, 0));
     }
-    h->head_done_for = -1;
+    h->carry.reset();
     if (rc) return rc;
-    h->prop_drawn_for = -1;
     // the log-posterior trace of these rows: one batched pass over the trace, behind the iterations
     if (count > 0) DISPATCH_D(h, h->D, rc = enqueue_hdp_logp_batch<DD>(h, first, count));
     return rc;

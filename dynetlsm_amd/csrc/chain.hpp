@@ -88,6 +88,23 @@ struct HdpDeviceState {
     double mbar_total, mbar_positive, m00_total, m_rest_total, override_total;
 };
 
+// What one sweep carries over to the next on the same handle: the proposal buffers of the pipelined sweep
+// enqueued last (valid for a pipelined sweep only), the iteration whose proposals an earlier launch has
+// already drawn into them, and the iteration whose head (the proposal pass and the first, evaluate-only
+// launch) is enqueued already - on the HDP-LPCM loop's second queue (capi_hdp.hpp)
+struct SweepCarry {
+    ProposeBuf next_prop{}; bool next_prop_ok = false;
+    long prop_drawn_for = -1, head_done_for = -1;
+    void reset() { next_prop_ok = false; prop_drawn_for = -1; head_done_for = -1; }
+    // were iteration `it`'s proposals (it < 0: counted on the device - never) drawn into these buffers
+    bool drawn(long it, const ProposeBuf &nb) const {
+        return it >= 0 && prop_drawn_for == it && next_prop_ok && next_prop.prop == nb.prop &&
+               next_prop.sync == nb.sync && next_prop.queue0 == nb.queue0 && next_prop.lsm_draw == nb.lsm_draw;
+    }
+    // a pipelined sweep has taken the buffers `nb` (and whatever was drawn ahead into them)
+    void taken(const ProposeBuf &nb) { next_prop = nb; next_prop_ok = true; prop_drawn_for = -1; }
+};
+
 struct ProfileSlot {
     double ms = 0.0;
     int launches = 0;
@@ -101,20 +118,13 @@ struct dlsm_chain {
     int T = 0, N = 0, D = 0, model = 0, squared = 0;
     uint64_t seed = 0; uint32_t chain = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;          // second queue of the speculative sweep
     void *stage = nullptr;                  // pinned host staging for the small copies of the C-ABI
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
     // HDP-LPCM loop, undirected: the intercept's likelihood pass on a queue of its own beside the label
     // update and the conjugate draws, handed over through device flags (kernels_hdploop.hpp, HdpFork)
     hipStream_t fork_stream = nullptr; hipEvent_t fork_ev = nullptr;
     int32_t *fork_flags = nullptr; int32_t fork_ticket = 0; bool fork_armed = false;
     int32_t *fork_err_host = nullptr, *fork_err_dev = nullptr;      // sticky error word (mapped host memory)
     bool fork_wait_value = false;           // the queues' waits are hipStreamWaitValue32 (else the gate kernel)
-    bool ll_beside_chain = false;           // the next undirected likelihood pass runs on the second queue
-    // the pipelined sweep in two pieces (HDP-LPCM loop on two queues): sweep_part 1 = its head only (the
-    // proposal pass and the first, evaluate-only launch - neither reads what the conjugate draws produce);
-    // head_done_for = the iteration whose head has been enqueued already (the sweep proper skips it)
-    int sweep_part = 0; long head_done_for = -1;
     // network
     int W = 0;
     uint32_t *ybits = nullptr, *ytbits = nullptr;
@@ -153,15 +163,7 @@ struct dlsm_chain {
     // sweep v2 scratch
     double *spec = nullptr; size_t spec_cap = 0;
     double *pipe = nullptr; size_t pipe_cap = 0;        // pipelined sweep (algo 4) buffers
-    // the proposal buffers of the sweep enqueued last (valid for a pipelined sweep only) and the
-    // iteration whose proposals the previous iteration's last launch has already drawn into them
-    // the centring sums riding in the pipelined sweep's last launch (k_pipe_last_ride): asked for by
-    // the undirected loops before they enqueue the sweep, granted (done) by launch_sweep_pipe
-    bool post_ride_want = false, post_ride_done = false;
-    bool loop_draws_intercept = false;      // set by the undirected LSM loop around its sweep
-    const double *post_ride_xref = nullptr;
-    int post_ride_jl = -1, post_ride_par = 0, post_ride_nwg = 0;
-    dlsm::ProposeBuf next_prop{}; bool next_prop_ok = false, pipe_touched = false; long prop_drawn_for = -1;
+    dlsm::SweepCarry carry;
     int n_cu = 256;
     int32_t *nctrl = nullptr; size_t nctrl_cap = 0;     // valid controls per (t, i, dir)
     bool nctrl_valid = false;
