@@ -12,6 +12,7 @@ from .hdp_lpcm import DynamicNetworkHDPLPCM  # noqa
 from .lpcm import DynamicNetworkLPCM  # noqa
 from .case_control import DirectedCaseControlSampler  # noqa
 from . import metrics  # noqa
+from . import model_selection  # noqa
 from .gof import posterior_predictive_check, GofResult  # noqa
 from .ic import information_criteria, compare_information_criteria, ICResult  # noqa
 

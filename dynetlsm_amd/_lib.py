@@ -161,6 +161,11 @@ SIGNATURES = {
     'dlsm_gof_observed': (C.c_int, [handle_t, c_u32_p, c_i64_p]),
     'dlsm_ic_accumulate': (C.c_int, [handle_t, c_u32_p, c_double_p, c_double_p, c_double_p, C.c_int,
                                      c_double_p, c_double_p, c_double_p]),
+    'dlsm_set_missing': (C.c_int, [handle_t, c_i32_p, C.c_int64]),
+    'dlsm_impute_missing': (C.c_int, [handle_t, C.c_uint32, C.c_int]),
+    'dlsm_missing_sampling': (C.c_int, [handle_t, C.c_int, C.c_int]),
+    'dlsm_get_missing': (C.c_int, [handle_t, c_double_p, c_u32_p, c_i64_p]),
+    'dlsm_reset_missing_sums': (C.c_int, [handle_t]),
     'dlsm_host_sample_tables': (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p,
                                           C.c_double, C.c_double, C.c_double, c_i64_p]),
     'dlsm_profile_enable': (C.c_int, [handle_t, C.c_int]),

@@ -31,6 +31,7 @@
 #include "kernels_forecast.hpp"
 #include "kernels_gof.hpp"
 #include "kernels_ic.hpp"
+#include "kernels_missing.hpp"
 #include "host_draws.hpp"
 
 using namespace dlsm;
@@ -606,7 +607,8 @@ void dlsm_destroy(dlsm_chain *h) {
                     h->lab_nk, h->lab_w, h->spec, h->nctrl, h->stamps, h->lsm, h->trace_X, h->trace_ic,
                     h->trace_logp, h->hops, h->hops_max, h->pipe, h->post_zt, h->post_cooc,
                     h->trace_radii, h->hdp, h->hdp_buf, h->htr_mu, h->htr_sigma, h->htr_beta,
-                    h->htr_w, h->htr_lambda, h->htr_hyper, h->htr_z, h->xr, h->cc_terms, h->cc_pos, h->cc_order};
+                    h->htr_w, h->htr_lambda, h->htr_hyper, h->htr_z, h->xr, h->cc_terms, h->cc_pos, h->cc_order,
+                    h->miss_jobs, h->miss_cols, h->miss_slot, h->miss_psum, h->miss_ones, h->miss_nacc};
     for (void *p : ptrs) if (p) hipFree(p);
     if (h->hsmall) hipHostFree(h->hsmall);
     if (h->timer0) hipEventDestroy(h->timer0);
@@ -665,8 +667,8 @@ int dlsm_upload_network(dlsm_chain *h, const double *Y) {
     hipMemcpy(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost);
     hipFree(dY); hipFree(dflag);
     HIPCHK(h, hipGetLastError());
-    if (flag) FAIL(h, DLSM_E_DATA, "network has entries other than 0.0 / 1.0 "
-                                   "(missing-edge sampling is not supported)");
+    if (flag) FAIL(h, DLSM_E_DATA, "network has entries other than 0.0 / 1.0 (impute the -1 coded dyads once "
+                                   "before the upload and list them with dlsm_set_missing to have them sampled)");
     { int rc = build_colmajor(h); if (rc) return rc; }
     h->have_network = true;
     h->have_hops = false;
@@ -1825,6 +1827,8 @@ int dlsm_trace_alloc(dlsm_chain *h, int n_total, double logp0) {
 
 }  // extern "C"
 
+#include "capi_missing.hpp"
+
 // The directed models' steps behind the sweep (lsm.py:520-572, hdp_lpcm.py:855-874 with is_directed): centring,
 // intercept_in, intercept_out and the radii, around three likelihood passes (case-control: two).
 //   xref, n_iter_procrustes: the centring pass's Procrustes reference (NULL: none)
@@ -1973,10 +1977,15 @@ static int enqueue_lsm_iteration(dlsm_chain *h, const Call &c, int it, bool coun
     int rc = enqueue_sweep<DD>(h, sc, ir, h->lsm_cfg.sweep_algo); if (rc) return rc;
     const bool ride_next = draw_next && !counter;
     if (h->model != DLSM_UNDIRECTED)
-        return enqueue_directed_steps<DD>(h, c, ir, xref, nip, ride_next, 0, alloc_only);
-    if (sc.rode && draw_next && h->carry.next_prop_ok && h->carry.next_prop.lsm_draw && c.knobs.post_fuse)
-        return enqueue_lsm_fused_finalize<DD>(h, c, ir, xref, sc);
-    return enqueue_lsm_plain_finalize<DD>(h, c, ir, xref, sc, ride_next);
+        rc = enqueue_directed_steps<DD>(h, c, ir, xref, nip, ride_next, 0, alloc_only);
+    else if (sc.rode && draw_next && h->carry.next_prop_ok && h->carry.next_prop.lsm_draw && c.knobs.post_fuse)
+        rc = enqueue_lsm_fused_finalize<DD>(h, c, ir, xref, sc);
+    else
+        rc = enqueue_lsm_plain_finalize<DD>(h, c, ir, xref, sc, ride_next);
+    if (rc || alloc_only) return rc;
+    // the missing dyads, from the state the trace row holds, for the next iteration to condition on (the
+    // proposals a tail has drawn ahead do not read the network)
+    return enqueue_impute_in_loop<DD>(h, h->stream, ir);
 }
 
 extern "C" {
@@ -1990,6 +1999,7 @@ int dlsm_lsm_run(dlsm_chain *h, int first, int count, int procrustes_ref) {
     NEED(h, procrustes_ref < h->trace_n, "procrustes_ref out of the trace");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = check_ready_sweep(h); if (rc) return rc;
+    if (h->miss_on) { rc = miss_check_ready(h); if (rc) return rc; }
     if (count == 0) return DLSM_OK;
     // Replay path (opt-in, DLSM_GRAPH=1): one iteration captured into a hipGraph, so an
     // iteration costs the host one call instead of ~40 launches; kernel arguments are

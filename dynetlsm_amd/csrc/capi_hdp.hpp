@@ -370,6 +370,8 @@ int dlsm_hdp_trace_alloc(dlsm_chain *h, int n_total, double logp0) {
 int dlsm_hdp_run(dlsm_chain *h, int first, int count) {
     NEED(h, h != nullptr, "null handle");
     NEED(h, h->hdp_configured && h->trace_X && h->htr_z, "configure the loop and allocate its trace first");
+    NEED(h, !h->miss_on, "missing-dyad sampling is switched on: this loop has no imputation step (drive the "
+                         "iterations from the host and call dlsm_impute_missing)");
     NEED(h, h->hdp_K == h->K && h->htr_K == h->K, "n_components changed since dlsm_hdp_configure");
     NEED(h, first >= 1 && count >= 0 && first + count <= h->trace_n && first + count <= h->htr_n,
          "iteration range out of the trace");

@@ -190,6 +190,12 @@ struct dlsm_chain {
     // one captured Gibbs iteration (hipGraph), replayed by dlsm_lsm_run
     hipGraph_t graph = nullptr; hipGraphExec_t graph_exec = nullptr;
     int graph_ref = -2, graph_algo = -1; bool graph_failed = false;
+    // missing-dyad imputation (kernels_missing.hpp): per-(matrix, t, row) segments of the list in both
+    // orientations, the accumulators per listed dyad, and whether dlsm_lsm_run ends its iterations with the step
+    int64_t miss_n = 0; int miss_njobs = 0;
+    int32_t *miss_jobs = nullptr, *miss_cols = nullptr, *miss_slot = nullptr;
+    double *miss_psum = nullptr; uint32_t *miss_ones = nullptr; unsigned long long *miss_nacc = nullptr;
+    bool miss_on = false; int64_t miss_after = 0;
     // measurement
     bool profiling = false;
     dlsm::ProfileSlot prof[DLSM_K_COUNT];

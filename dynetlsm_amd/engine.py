@@ -45,6 +45,29 @@ def pack_network(Y):
     return np.ascontiguousarray(bytes_).view('<u4').astype(np.uint32).reshape(T, N, W)
 
 
+def check_missing_index(index, T, N, model):
+    """(n, 3) int32 rows (t, i, j) of missing dyads, validated as ``dlsm_set_missing`` validates them
+    (ValueError, before any device call)"""
+    idx = np.asarray(index)
+    if idx.size == 0:
+        return np.zeros((0, 3), dtype=np.int32)
+    if idx.ndim != 2 or idx.shape[1] != 3 or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError('missing dyads must be an (n, 3) integer array of (t, i, j) rows')
+    if model == DIRECTED_CASE_CONTROL:
+        raise ValueError('case-control chains hold edge lists: missing dyads cannot be sampled')
+    t, i, j = idx[:, 0], idx[:, 1], idx[:, 2]
+    if (t < 0).any() or (t >= T).any() or (idx[:, 1:] < 0).any() or (idx[:, 1:] >= N).any():
+        raise ValueError('missing dyad outside T=%d, N=%d' % (T, N))
+    if model == UNDIRECTED and (i >= j).any():
+        raise ValueError('undirected missing dyads are listed with i < j')
+    if (i == j).any():
+        raise ValueError('the diagonal is not a dyad')
+    key = (t.astype(np.int64) * N + i) * N + j
+    if np.unique(key).shape[0] != key.shape[0]:
+        raise ValueError('a missing dyad is listed twice')
+    return np.ascontiguousarray(idx, dtype=np.int32)
+
+
 def _f64(a, shape=None, name='array'):
     a = np.ascontiguousarray(a, dtype=np.float64)
     if shape is not None and tuple(a.shape) != tuple(shape):
@@ -212,6 +235,36 @@ class Chain(object):
     def resample_controls(self, it, n_control):
         self._ck(self._L.dlsm_resample_controls(self._h, int(it), int(n_control)))
         self.C = int(n_control)
+
+    # -- missing dyads -------------------------------------------------------
+    def set_missing(self, index):
+        """the missing dyads as (n, 3) rows (t, i, j): i < j for the undirected model, i != j for the
+        directed one; an empty list clears them.  Checked here, before any device call, and again by
+        the engine."""
+        idx = check_missing_index(index, self.T, self.N, self.model)
+        self._ck(self._L.dlsm_set_missing(self._h, _p(idx) if idx.shape[0] else None, idx.shape[0]))
+        self.n_missing = int(idx.shape[0])
+
+    def impute_missing(self, it, accumulate=False):
+        """draw every missing dyad from its conditional at the current state (the draws of iteration
+        ``it``) into the chain's network; asynchronous"""
+        self._ck(self._L.dlsm_impute_missing(self._h, int(it), int(bool(accumulate))))
+
+    def missing_sampling(self, on=True, accumulate_after=0):
+        """``lsm_run`` ends every iteration with the step; it accumulates when it > accumulate_after"""
+        self._ck(self._L.dlsm_missing_sampling(self._h, int(bool(on)), int(accumulate_after)))
+
+    def get_missing(self):
+        """(p_sum (n,), ones (n,) uint32, n_accumulated) in the order of ``set_missing``'s list"""
+        n = getattr(self, 'n_missing', 0)
+        ps = np.zeros(n)
+        ones = np.zeros(n, dtype=np.uint32)
+        k = C.c_int64(0)
+        self._ck(self._L.dlsm_get_missing(self._h, _p(ps), ones.ctypes.data_as(_lib.c_u32_p), C.byref(k)))
+        return ps, ones, int(k.value)
+
+    def reset_missing_sums(self):
+        self._ck(self._L.dlsm_reset_missing_sums(self._h))
 
     # -- state -------------------------------------------------------------
     def set_positions(self, X):

@@ -24,9 +24,9 @@ from . import posterior as post
 from . import forecast as fc
 from .diagnostics import geweke_diag
 from .imputer import SimpleNetworkImputer
-from .metrics import FittedQuantities
+from .metrics import FittedQuantities, missing_index
 from .lsm import (DynamicNetworkLSM, _ScalarMetropolis, _dirichlet_logpdf,
-                  check_random_state)
+                  _missing_attributes, check_random_state)
 
 __all__ = ['DynamicNetworkHDPLPCM']
 
@@ -75,8 +75,9 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
                  mean_variance_prior_std=4.0, step_size_X='auto', step_size_intercept=0.1,
                  step_size_radii=175000, n_control=None, n_resample_control=100, copy=True,
                  random_state=None, device=0, chain_id=0, sweep_algo=0, hdp_loop='auto',
-                 post_processing='auto'):
+                 post_processing='auto', sample_missing=False):
         self.n_iter = n_iter
+        self.sample_missing = sample_missing
         self.hdp_loop = hdp_loop
         self.is_directed = is_directed
         self.n_features = n_features
@@ -214,12 +215,24 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
         # missing dyads (hdp_lpcm.py:669-706): imputed once; undirected models also average
         # per-iteration Bernoulli draws of them after burn-in into ``missings_``
         self.nan_mask_, miss = None, None
+        if self.sample_missing and self.n_control is not None:
+            raise ValueError('sample_missing=True is not supported with n_control: the case-control '
+                             'chain holds edge lists and control samples, not the dyads to re-draw')
+        if self.sample_missing and self.hdp_loop == 'device':
+            raise ValueError("sample_missing=True runs on the host-driven loop: hdp_loop='device' "
+                             'has no imputation step')
+        # sample_missing=True: the dyads are drawn on the device instead and written into the chain's
+        # network (Chain.impute_missing), from the host-driven loop; no host draws then
+        self._miss_index = None
+        if self.sample_missing and np.any(Y == -1):
+            self._miss_index = missing_index(Y, self.is_directed)
         if np.any(Y == -1):
             if not self.is_directed:
-                miss = np.nonzero(np.triu(Y == -1, 1))            # (t, i, j), row-major
                 iu = np.nonzero(np.triu(np.ones(Y.shape, dtype=bool), 1))
                 self.nan_mask_ = Y[iu] == -1
-                self.missings_ = np.zeros(miss[0].shape[0])
+                if self._miss_index is None:
+                    miss = np.nonzero(np.triu(Y == -1, 1))        # (t, i, j), row-major
+                    self.missings_ = np.zeros(miss[0].shape[0])
             else:
                 off = np.nonzero(~np.eye(Y.shape[1], dtype=bool)[None].repeat(Y.shape[0], 0))
                 self.nan_mask_ = Y[off] == -1
@@ -308,6 +321,9 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
         self.loop_kind_ = ('device-resident' if (self.hdp_loop == 'device' or
                                                  (self.hdp_loop == 'auto' and not self.is_directed))
                            else 'host-driven')
+        if self._miss_index is not None:
+            self.loop_kind_ = 'host-driven'
+            chain.set_missing(self._miss_index)
         # The device-resident loop keeps its trace in HBM; the three large arrays - Xs_
         # (320 KB per sample at T=10, N=2000), zs_, weights_ - reach the host only when somebody
         # reads them (__getattr__), and the post-loop processing runs where they lie.
@@ -448,6 +464,8 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
             X = chain.get_positions()
             mu, sigma, weights = mu.copy(), sigma.copy(), weights.copy()
             beta, lmbda = hu.gibbs_updates(sums, n, nk, mu, sigma, beta, weights, lmbda, hp, rng)
+            if self._miss_index is not None:      # hdp_lpcm.py:1039-1049, with the draw written back
+                chain.impute_missing(it, it > self.n_burn_)
             if miss is not None:                  # hdp_lpcm.py:1039-1049
                 dm = X[miss[0], miss[1]] - X[miss[0], miss[2]]
                 eta = intercept[0] - np.sqrt(np.sum(dm * dm, axis=1))
@@ -588,6 +606,8 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
                         self.missings_ += y_ij
         if self._miss is not None:
             self.missings_ /= max(1, n_total - self.n_burn_)       # hdp_lpcm.py:1155-1156
+        if self._miss_index is not None:
+            _missing_attributes(self, chain, self._miss_index)
         chain.get_samplers(self.latent_samplers)
         self.gamma, self.alpha_init, self.alpha, self.kappa = (hp.gamma, hp.alpha_init,
                                                                hp.alpha, hp.kappa)

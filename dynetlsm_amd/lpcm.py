@@ -20,9 +20,9 @@ from . import hdp_updates as hu
 from . import initialization as init_mod
 from . import posterior as post
 from .imputer import SimpleNetworkImputer
-from .metrics import FittedQuantities
+from .metrics import FittedQuantities, missing_index
 from .lsm import (DynamicNetworkLSM, _ScalarMetropolis, _dirichlet_logpdf,
-                  check_random_state)
+                  _missing_attributes, check_random_state)
 
 __all__ = ['DynamicNetworkLPCM']
 
@@ -38,8 +38,9 @@ class DynamicNetworkLPCM(FittedQuantities):
                  dirichlet_prior='uniform', sigma_prior_std=4.0, mean_variance_prior_std=4.0,
                  step_size_X='auto', step_size_intercept=0.1, step_size_radii=175000,
                  n_control=None, n_resample_control=100, copy=True, random_state=None,
-                 device=0, chain_id=0, sweep_algo=0):
+                 device=0, chain_id=0, sweep_algo=0, sample_missing=False):
         self.n_iter = n_iter
+        self.sample_missing = sample_missing
         self.is_directed = is_directed
         self.selection_type = selection_type
         self.n_features = n_features
@@ -156,14 +157,23 @@ class DynamicNetworkLPCM(FittedQuantities):
         T, N, _ = Y_raw.shape
         K, D = self.n_components, check_n_features(self.n_features)
         rng = check_random_state(self.random_state)
+        if self.sample_missing and self.n_control is not None:
+            raise ValueError('sample_missing=True is not supported with n_control: the case-control '
+                             'chain holds edge lists and control samples, not the dyads to re-draw')
         self.nan_mask_, miss = None, None
+        # sample_missing=True: the dyads are drawn on the device and written into the chain's network;
+        # no host draws then
+        miss_index = None
+        if self.sample_missing and np.any(Y_raw == -1):
+            miss_index = missing_index(Y_raw, self.is_directed)
         Y = Y_raw
         if np.any(Y_raw == -1):                            # lpcm.py:352-366
             if not self.is_directed:
-                miss = np.nonzero(np.triu(Y_raw == -1, 1))
                 iu = np.nonzero(np.triu(np.ones(Y_raw.shape, dtype=bool), 1))
                 self.nan_mask_ = Y_raw[iu] == -1
-                self.missings_ = np.zeros(miss[0].shape[0])
+                if miss_index is None:
+                    miss = np.nonzero(np.triu(Y_raw == -1, 1))
+                    self.missings_ = np.zeros(miss[0].shape[0])
             else:
                 off = np.nonzero(~np.eye(N, dtype=bool)[None].repeat(T, 0))
                 self.nan_mask_ = Y_raw[off] == -1
@@ -247,6 +257,8 @@ class DynamicNetworkLPCM(FittedQuantities):
         chain.set_prior_mixture(mu, sigma, lmbda, z)
         sums = hu.DeviceLabelSums(chain)
         store(0, chain.loglik_full())
+        if miss_index is not None:
+            chain.set_missing(miss_index)
         var = self.intercept_variance_prior
         t_loop = time.perf_counter()
         for it in range(1, n_total):
@@ -290,6 +302,8 @@ class DynamicNetworkLPCM(FittedQuantities):
             init_w, trans_w = init_w.copy(), trans_w.copy()
             lmbda = hu.lpcm_gibbs_updates(sums, n, nk, mu, sigma, init_w, trans_w, lmbda, hp,
                                           rng, self.dirichlet_prior_)
+            if miss_index is not None:               # lpcm.py:676-689, with the draw written back
+                chain.impute_missing(it, it > self.n_burn_)
             if miss is not None:                     # lpcm.py:676-689
                 dm = X[miss[0], miss[1]] - X[miss[0], miss[2]]
                 eta = intercept[0] - np.sqrt(np.sum(dm * dm, axis=1))
@@ -300,6 +314,8 @@ class DynamicNetworkLPCM(FittedQuantities):
         self.loop_seconds_ = time.perf_counter() - t_loop
         if miss is not None:
             self.missings_ /= max(1, n_total - self.n_burn_)
+        if miss_index is not None:
+            _missing_attributes(self, chain, miss_index)
         chain.get_samplers(self.latent_samplers)
         self.mean_variance_prior_, self.b_ = hp.mean_variance_prior, hp.b
 

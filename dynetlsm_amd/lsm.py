@@ -13,7 +13,9 @@ Differences from the reference that a user can see:
     (keyed by a seed drawn from ``random_state``) and the even/odd-t scan order,
     so chains are equal in distribution, not sample for sample;
   * missing edges (-1 coded dyads) are imputed once before the chain, as the reference
-    effectively does (see ``imputer``); NaN entries are rejected;
+    effectively does (see ``imputer``); with ``sample_missing=True`` the device loop then draws
+    them again from their conditional at the end of every iteration (data augmentation: the
+    chain targets the posterior given the observed dyads); NaN entries are rejected;
   * ``fit(Y, init=...)`` accepts starting values and skips the init pipeline.
 """
 import time
@@ -24,7 +26,7 @@ from scipy.special import gammaln, xlogy
 from .engine import Chain, SamplerGrid, check_n_features
 from . import initialization as init_mod
 from .imputer import SimpleNetworkImputer
-from .metrics import FittedQuantities
+from .metrics import FittedQuantities, missing_index
 
 __all__ = ['DynamicNetworkLSM']
 
@@ -37,6 +39,17 @@ def check_random_state(seed):
     if isinstance(seed, np.random.RandomState):
         return seed
     raise ValueError('%r cannot be used to seed a numpy.random.RandomState' % seed)
+
+
+def _missing_attributes(est, chain, index):
+    """``missing_index_``, ``missing_probas_`` and ``missings_`` of a ``sample_missing=True`` fit from
+    the chain's accumulators (NaN when no iteration beyond the burn-in accumulated)"""
+    p_sum, ones, k = chain.get_missing()
+    est.missing_index_ = index
+    est.n_missing_accumulated_ = k
+    with np.errstate(invalid='ignore', divide='ignore'):
+        est.missing_probas_ = p_sum / k if k else np.full(p_sum.shape, np.nan)
+        est.missings_ = ones / float(k) if k else np.full(p_sum.shape, np.nan)
 
 
 class _ScalarMetropolis(object):
@@ -87,15 +100,19 @@ class DynamicNetworkLSM(FittedQuantities):
 
     Constructor parameters are the reference's (lsm.py:234-268) plus
     ``device`` (GPU index), ``chain_id`` (Philox stream of this chain) and
-    ``sweep_algo`` (0 auto; 1 .. 5 as ``dlsm_sweep_positions`` in include/dynetlsm_hip.h)."""
+    ``sweep_algo`` (0 auto; 1 .. 5 as ``dlsm_sweep_positions`` in include/dynetlsm_hip.h).
+    ``sample_missing=True`` re-draws the -1 coded dyads on the device every iteration and leaves
+    ``missing_index_`` (n, 3), ``missing_probas_`` (post-burn-in mean of p_ij) and ``missings_``
+    (post-burn-in mean of the draws); ``Y_fit_`` stays the initial imputation."""
 
     def __init__(self, n_features=2, is_directed=False, n_iter=5000, tune=2500,
                  tune_interval=100, burn=2500, intercept_prior='auto',
                  intercept_variance_prior=2.0, tau_sq=2.0, sigma_sq=0.1, step_size_X=0.1,
                  step_size_intercept=0.1, step_size_radii=175000, n_control=None,
                  n_resample_control=100, copy=True, random_state=None, device=0,
-                 chain_id=0, sweep_algo=0, directed_loop='device'):
+                 chain_id=0, sweep_algo=0, directed_loop='device', sample_missing=False):
         self.directed_loop = directed_loop
+        self.sample_missing = sample_missing
         self.n_iter = n_iter
         self.is_directed = is_directed
         self.n_features = n_features
@@ -132,7 +149,13 @@ class DynamicNetworkLSM(FittedQuantities):
             raise ValueError('Y must have shape (n_time_steps, n_nodes, n_nodes)')
         if np.any(np.isnan(Y)):
             raise ValueError('NaN entries are not supported: code missing dyads as -1')
+        if self.sample_missing and self.n_control is not None:
+            raise ValueError('sample_missing=True is not supported with n_control: the case-control '
+                             'chain holds edge lists and control samples, not the dyads to re-draw')
+        miss_index = None
         if np.any(Y == -1):          # lsm.py:345-359
+            if self.sample_missing:
+                miss_index = missing_index(Y, self.is_directed)
             Y = SimpleNetworkImputer(strategy='random', missing_value=-1).fit_transform(Y)
         T, N, _ = Y.shape
         D = check_n_features(self.n_features)
@@ -204,6 +227,10 @@ class DynamicNetworkLSM(FittedQuantities):
         chain.set_samplers(self.latent_samplers)
         ll0 = chain.loglik_full()
         logp0 = self._log_prior(X, intercept, ip) + ll0
+        self._impute = miss_index is not None and miss_index.shape[0] > 0
+        if self._impute:             # lsm.py:525-545, with the draw written back
+            chain.set_missing(miss_index)
+            chain.missing_sampling(True, accumulate_after=self.n_burn_)
 
         t_loop = time.perf_counter()
         if not self.is_directed:
@@ -215,6 +242,9 @@ class DynamicNetworkLSM(FittedQuantities):
                                logp0, ip)
         chain.get_samplers(self.latent_samplers)
         self.loop_seconds_ = time.perf_counter() - t_loop     # Gibbs loop only
+        if self._impute:
+            _missing_attributes(self, chain, miss_index)
+            chain.missing_sampling(False)
         self._set_map(n_total)
         return self
 
@@ -354,6 +384,8 @@ class DynamicNetworkLSM(FittedQuantities):
             Xc = chain.get_positions()
             self.Xs_[it], self.intercepts_[it], self.radiis_[it] = Xc, intercept, radii
             self.logps_[it] = ll + self._log_prior(Xc, intercept, ip)
+            if self._impute:
+                chain.impute_missing(it, it > self.n_burn_)
 
     def _set_map(self, n_total):
         """MAP bookkeeping of lsm.py:554-566, replayed over the trace."""

@@ -3,7 +3,8 @@ edge probabilities and the variation of information between two partitions.  Hos
 O(T N^2 log) once per fitted model (scikit-learn's ``roc_auc_score``, as the reference)."""
 import numpy as np
 
-__all__ = ['network_auc', 'out_of_sample_auc', 'variation_of_information', 'FittedQuantities']
+__all__ = ['network_auc', 'out_of_sample_auc', 'variation_of_information', 'heldout_scores',
+           'missing_index', 'FittedQuantities']
 
 
 def _dyads(Y, is_directed):
@@ -34,6 +35,37 @@ def variation_of_information(labels_true, labels_pred):
     from sklearn.metrics.cluster import entropy
     return (entropy(labels_true) + entropy(labels_pred) -
             2 * mutual_info_score(labels_true, labels_pred))
+
+
+def missing_index(Y, is_directed):
+    """the -1 coded dyads of ``Y`` (T, N, N) as (n, 3) int64 rows (t, i, j), row-major; undirected:
+    the pairs i < j with either entry coded"""
+    M = np.asarray(Y) == -1
+    N = M.shape[1]
+    if is_directed:
+        M = M & ~np.eye(N, dtype=bool)
+    else:
+        M = np.triu(M | M.swapaxes(1, 2), 1)
+    return np.stack(np.nonzero(M), axis=1).astype(np.int64)
+
+
+def heldout_scores(model, Y_true):
+    """AUC and mean log-loss of ``model.missing_probas_`` (a ``sample_missing=True`` fit) against the
+    true values of the held-out dyads ``model.missing_index_`` in ``Y_true`` (T, N, N).  The AUC is
+    NaN when the held-out dyads are all of one class."""
+    if not hasattr(model, 'missing_probas_'):
+        raise ValueError('heldout_scores needs a fit with sample_missing=True on a network with -1 dyads')
+    idx = model.missing_index_
+    y = np.asarray(Y_true)[idx[:, 0], idx[:, 1], idx[:, 2]]
+    if not np.isin(y, (0, 1)).all():
+        raise ValueError('Y_true must hold 0 / 1 at the held-out dyads')
+    p = np.clip(model.missing_probas_, 1e-15, 1 - 1e-15)
+    log_loss = float(-np.mean(np.where(y == 1, np.log(p), np.log1p(-p))))
+    auc = float('nan')
+    if 0 < y.sum() < y.shape[0]:
+        from sklearn.metrics import roc_auc_score
+        auc = float(roc_auc_score(y, model.missing_probas_))
+    return {'auc': auc, 'log_loss': log_loss, 'n': int(y.shape[0])}
 
 
 class FittedQuantities(object):

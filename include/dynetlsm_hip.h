@@ -420,6 +420,38 @@ int dlsm_ic_accumulate(dlsm_chain *h, const uint32_t *bits, const double *Xs, co
                        const double *radii, int S, double *totals, double *sample_loglik,
                        double *pointwise);
 
+/* ---- missing dyads: the data-augmentation step --------------------------- */
+/* lsm.py:525-545 / hdp_lpcm.py:1025-1049 draw y_ij ~ Bernoulli(p_ij) for the -1 coded dyads every
+ * iteration (their write-back into the network is lost in a fancy-index copy; hdp_lpcm.py:1155-1156
+ * averages the draws into missings_).  Here the draw lands in every copy of the packed network, so the
+ * next sweep and likelihood pass condition on it: the chain targets the posterior given the observed
+ * dyads alone.  The uniform of a dyad is Philox4x32-10 keyed by the chain's seed at counter
+ * (min(i,j) | (t & 255) << 24, max(i,j) | (t >> 8) << 24, iteration, chain << 8 | 8): an undirected
+ * dyad takes the first 53-bit uniform, the arc i -> j the first when i < j and the second otherwise;
+ * bit = u < p, p = expit(b - d) or the directed model of metrics.py:57-60.  A draw depends on (seed,
+ * chain, iteration, t, pair) alone. */
+/* the missing dyads (lsm.py:345-359's nan mask as a list): n triples (t, i, j), i < j for the undirected
+ * model, i != j for the directed one; n = 0 clears the list and switches the sampling off.  Needs the
+ * network uploaded (the estimators impute the -1 entries once for it, imputer.py).  An entry out of
+ * range, off its triangle or listed twice -> DLSM_E_DATA; a case-control chain (it holds edge lists)
+ * -> DLSM_E_ARG; N >= 2^24 or n >= 2^30 -> DLSM_E_LIMIT.  Zeroes the accumulators. */
+int dlsm_set_missing(dlsm_chain *h, const int32_t *tij, int64_t n);
+/* one step (lsm.py:525-545, hdp_lpcm.py:1039-1049) at the handle's current positions, intercepts and
+ * radii with the draws of iteration `iter`; accumulate != 0 adds p and the drawn bit of every dyad to
+ * the accumulators.  Enqueued on the handle's stream. */
+int dlsm_impute_missing(dlsm_chain *h, uint32_t iter, int accumulate);
+/* on != 0: dlsm_lsm_run ends every iteration `it` with the step, after the trace row of `it` is written
+ * and from exactly the state that row stores (lsm.py:525-545 sits at the same place of the loop), and
+ * accumulates when it > accumulate_after (hdp_lpcm.py:1046: the burn-in; < 0: always).  While it is on
+ * dlsm_hdp_run returns DLSM_E_ARG: that loop has no imputation step. */
+int dlsm_missing_sampling(dlsm_chain *h, int on, int accumulate_after);
+/* the accumulators in the order of the list given to dlsm_set_missing: p_sum n (sum of p_ij), ones n
+ * (drawn ones: hdp_lpcm.py:1046-1049's missings_ before its division), n_accumulated the steps that
+ * accumulated; any pointer may be NULL.  Waits for the handle's stream. */
+int dlsm_get_missing(dlsm_chain *h, double *p_sum, uint32_t *ones, int64_t *n_accumulated);
+/* zero the accumulators and the step count (hdp_lpcm.py:699-706 allocates missings_ as zeros) */
+int dlsm_reset_missing_sums(dlsm_chain *h);
+
 /* ---- host-stream auxiliary draws ----------------------- */
 /* sample_tables (sample_auxillary.py:6-28): m T*K*K int64 = tables per (restaurant, dish)
  * given the transition counts n T*K*K (n[0,0,:] = initial counts) and beta K.  The
