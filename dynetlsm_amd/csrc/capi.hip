@@ -2216,36 +2216,25 @@ extern "C" int dlsm_host_sample_tables(void *numpy_bitgen, int T, int K, const d
 }
 
 #ifdef DLSM_PIPE_TIMING
-extern "C" int dlsm_debug_pipe_timing(unsigned long long *items, unsigned long long *res) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(items, HIP_SYMBOL(dlsm::g_pipe_item_t), sizeof(dlsm::g_pipe_item_t)) != hipSuccess) return -2;
-    if (hipMemcpyFromSymbol(res, HIP_SYMBOL(dlsm::g_pipe_res_t), sizeof(dlsm::g_pipe_res_t)) != hipSuccess) return -3;
-    return 0;
-}
-extern "C" int dlsm_debug_ccpipe_timing(unsigned long long *res, unsigned long long *items) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(res, HIP_SYMBOL(dlsm::g_cc_res_t), sizeof(dlsm::g_cc_res_t)) != hipSuccess) return -2;
-    if (hipMemcpyFromSymbol(items, HIP_SYMBOL(dlsm::g_cc_item_t), sizeof(dlsm::g_cc_item_t)) != hipSuccess) return -3;
-    return 0;
-}
-extern "C" int dlsm_debug_labels_timing(unsigned long long *waves) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(waves, HIP_SYMBOL(dlsm::g_lab_t), sizeof(dlsm::g_lab_t)) != hipSuccess) return -2;
-    return 0;
-}
-extern "C" int dlsm_debug_hdp_globals_phases(unsigned long long *out) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dlsm::g_hdp_phase), sizeof(dlsm::g_hdp_phase)) != hipSuccess) return -2;
-    return 0;
-}
-extern "C" int dlsm_debug_hdp_tail_timing(unsigned long long *out) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dlsm::g_hdp_t), sizeof(dlsm::g_hdp_t)) != hipSuccess) return -2;
-    return 0;
-}
-extern "C" int dlsm_debug_loglik_timing(unsigned long long *waves) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(waves, HIP_SYMBOL(dlsm::g_ll_t), sizeof(dlsm::g_ll_t)) != hipSuccess) return -2;
-    return 0;
+// The reader of kernel_stamps.hpp's arrays (profiles/stamps.py): `bytes` is the size the caller expects, checked
+// before anything touches the device.  -1 unknown name, -2 stale size, -3 / -4 the device.
+extern "C" int dlsm_debug_read_stamps(const char *name, void *out, size_t bytes) {
+    static const struct { const char *name; const void *symbol; size_t bytes; } arrays[] = {
+        {"pipe_item_t", HIP_SYMBOL(dlsm::g_pipe_item_t), sizeof(dlsm::g_pipe_item_t)},
+        {"pipe_res_t", HIP_SYMBOL(dlsm::g_pipe_res_t), sizeof(dlsm::g_pipe_res_t)},
+        {"cc_res_t", HIP_SYMBOL(dlsm::g_cc_res_t), sizeof(dlsm::g_cc_res_t)},
+        {"cc_item_t", HIP_SYMBOL(dlsm::g_cc_item_t), sizeof(dlsm::g_cc_item_t)},
+        {"lab_t", HIP_SYMBOL(dlsm::g_lab_t), sizeof(dlsm::g_lab_t)},
+        {"ll_t", HIP_SYMBOL(dlsm::g_ll_t), sizeof(dlsm::g_ll_t)},
+        {"hdp_t", HIP_SYMBOL(dlsm::g_hdp_t), sizeof(dlsm::g_hdp_t)},
+        {"hdp_phase", HIP_SYMBOL(dlsm::g_hdp_phase), sizeof(dlsm::g_hdp_phase)},
+    };
+    for (const auto &a : arrays) {
+        if (!name || !out || strcmp(name, a.name) != 0) continue;
+        if (bytes != a.bytes) return -2;
+        if (hipDeviceSynchronize() != hipSuccess) return -3;
+        return hipMemcpyFromSymbol(out, a.symbol, a.bytes) == hipSuccess ? 0 : -4;
+    }
+    return -1;
 }
 #endif

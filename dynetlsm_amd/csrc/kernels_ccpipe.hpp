@@ -324,14 +324,8 @@ _Pragma("unroll")                                                               
         }
 
 // Resolve batch b of slice t: thread k owns node k of the batch.
-#ifdef DLSM_PIPE_TIMING
-// resolver phase stamps and evaluator entry / exit of the last sweep (profiles/ccpipe_timing.py)
-__device__ unsigned long long g_cc_res_t[32][16][8];
-__device__ unsigned long long g_cc_item_t[32][4096][2];
-#define DLSM_CC_STAMP(I_, DEP_) { unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "v"(DEP_)); cts[I_] = t_; }
-#else
-#define DLSM_CC_STAMP(I_, DEP_)
-#endif
+// (resolver phase stamps - CC_RES_T: one row per slice, slots 1 and 7 its helper's - and evaluator entry / exit -
+// CC_ITEM_T - of the last sweep: kernel_stamps.hpp; profiles/ccpipe_timing.py reads them)
 // One wavefront's arrival at its workgroup's barrier, as the instruction (see ccpipe_resolve): the
 // "memory" clobber keeps the compiler from moving LDS / global accesses across it; loads already
 // requested stay in flight (gfx950 needs no drained counters at s_barrier).
@@ -345,17 +339,11 @@ template <int D>
 __device__ __forceinline__ void ccpipe_resolve(const ChainView &c, const CcPipeBuf &pb, int b, int t,
                                                unsigned long long (*sMask)[CP_WAVES],
                                                unsigned long long *sPrev, int *sChanged,
-                                               double *sCross, double (*sOv)[CP_B], int (*sOi)[CP_B]
-#ifdef DLSM_PIPE_TIMING
-                                               , int tl
-#endif
-                                               ) {
+                                               double *sCross, double (*sOv)[CP_B], int (*sOi)[CP_B],
+                                               Stamps<CC_RES_T> cst) {
     constexpr int PW = 2 * D + 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef DLSM_PIPE_TIMING
-    unsigned long long cts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    DLSM_CC_STAMP(0, (double)tid)
+    DLSM_STAMP(cst, 0, (double)tid)
     const int N = c.N;
     const int j0 = b * CP_B;
     const int nb = min(CP_B, N - j0);
@@ -457,7 +445,7 @@ __device__ __forceinline__ void ccpipe_resolve(const ChainView &c, const CcPipeB
         }
         cc_barrier_arrive_after_lds_stores();          // (the upper half's barrier; sPrev is this half's store)
     }
-    DLSM_CC_STAMP(2, r)
+    DLSM_STAMP(cst, 2, r)
     // the node's first own entries stay in registers through the passes
 #pragma unroll
     for (int e = 0; e < CP_OWN_REGS; ++e) oi[e] = e < nown ? oi[e] : 0;
@@ -489,7 +477,7 @@ __device__ __forceinline__ void ccpipe_resolve(const ChainView &c, const CcPipeB
     if (!upper && lane == 0) { sW[wave] = mine; sCtl[1 + wave] = -1; }
     if (tid == 0) sCtl[0] = 0;
     __syncthreads();
-    DLSM_CC_STAMP(3, ov[0])
+    DLSM_STAMP(cst, 3, ov[0])
     if (!upper) {
         int computed_v = -2, filed_v = -2;                  // version my last pass was based on / I have filed
         bool quiet = false;                                 // ... and that pass changed nothing
@@ -559,9 +547,7 @@ __device__ __forceinline__ void ccpipe_resolve(const ChainView &c, const CcPipeB
                     __hip_atomic_fetch_add(&sCtl[0], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
-#ifdef DLSM_PIPE_TIMING
-            cts[6] += 1;
-#endif
+            cst.set(6, cst.get(6) + 1);         // (slot 6 counts the trips of the loop)
         }
         // the spin bound ran out: the mask a wavefront holds is NOT the fixed point - say so.  (Through a pointer
         // held in device memory, read here only: the launch's own error word, pb.err, kept alive across this loop
@@ -573,7 +559,7 @@ __device__ __forceinline__ void ccpipe_resolve(const ChainView &c, const CcPipeB
     }
 #undef CC_LD64
 #undef CC_LD32
-    DLSM_CC_STAMP(4, (double)lane)
+    DLSM_STAMP(cst, 4, (double)lane)
     const int accepted = (int)((mine >> lane) & 1ull);
     if (valid) {
         const size_t tj = (size_t)t * N + j0 + k;
@@ -588,10 +574,8 @@ __device__ __forceinline__ void ccpipe_resolve(const ChainView &c, const CcPipeB
         c.step[tj] = st; c.nacc[tj] = na; c.nsteps[tj] = ns; c.until[tj] = un;
     }
     if (!upper && lane == 0) accg[wave] = mine;
-#ifdef DLSM_PIPE_TIMING
-    DLSM_CC_STAMP(5, (double)lane)
-    if (tid == 0 && tl >= 0 && tl < 32 && t < 16) for (int i = 0; i < 7; ++i) if (i != 1) g_cc_res_t[tl][t][i] = cts[i];   // ([1], [7]: the helper's)
-#endif
+    DLSM_STAMP(cst, 5, (double)lane)
+    if (tid == 0) cst.flush(0x7du);                     // (slots 1 and 7 of the row are the helper's)
 }
 
 // The helper of slice t's resolver: the cross sums of batch b (cc_cross_loads / _sums above) on a CU of its own.
@@ -604,16 +588,9 @@ __device__ __forceinline__ void ccpipe_resolve(const ChainView &c, const CcPipeB
 // sweep's first launch, which resolves nothing, empties every slot.
 template <int D>
 __device__ __forceinline__ void ccpipe_cross_helper(const ChainView &c, const CcPipeBuf &pb, int b, int t,
-                                                    unsigned long long *sPrev
-#ifdef DLSM_PIPE_TIMING
-                                                    , int tl
-#endif
-                                                    ) {
+                                                    unsigned long long *sPrev, Stamps<CC_RES_T> cst) {
     const int tid = threadIdx.x;
-#ifdef DLSM_PIPE_TIMING
-    unsigned long long cts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    DLSM_CC_STAMP(1, (double)tid)
-#endif
+    DLSM_STAMP(cst, 1, (double)tid)
     const int nb = min(CP_B, c.N - b * CP_B);
     const int bb = b & 1;
     if (tid < CP_WAVES) sPrev[tid] = b > 0 ? pb.accmask[(size_t)t * CP_WAVES + tid] : 0ull;
@@ -626,10 +603,8 @@ __device__ __forceinline__ void ccpipe_cross_helper(const ChainView &c, const Cc
         cc_barrier_arrive_after_lds_stores();           // sPrev (wavefront 0's store) visible; the 48 loads stay in flight
         cc_cross_sums
         coh_store<true>(&pb.xsum[(size_t)t * CP_B + k], xs);       // (an 8-byte store past the L1: the announcement)
-#ifdef DLSM_PIPE_TIMING
-        DLSM_CC_STAMP(7, xs)
-        if (tid == 0 && tl >= 0 && tl < 32 && t < 16) { g_cc_res_t[tl][t][1] = cts[1]; g_cc_res_t[tl][t][7] = cts[7]; }
-#endif
+        DLSM_STAMP(cst, 7, xs)
+        if (tid == 0) cst.flush(1u << 1 | 1u << 7);     // (its two slots of the resolver's row)
     } else {                                            // (the workgroup's other eight wavefronts: an arrival only)
         cc_barrier_arrive();
     }
@@ -653,22 +628,15 @@ __global__ __launch_bounds__(CP_THREADS) void k_ccpipe_step(ChainView c, CcPipeB
         // (the sweep's first launch resolves nothing: it empties the helpers' hand-over slots)
         if (l < 0 && pb.helpers && (int)threadIdx.x < CP_B)
             pb.xsum[(size_t)t * CP_B + threadIdx.x] = __longlong_as_double((long long)CC_XS_EMPTY);
-        if (b >= 0 && b < pb.nbat) ccpipe_resolve<D>(c, pb, b, t, sMask, sPrev, sChanged, sCross, sOv, sOi
-#ifdef DLSM_PIPE_TIMING
-                                                     , l + 1
-#endif
-                                                     );
+        if (b >= 0 && b < pb.nbat) ccpipe_resolve<D>(c, pb, b, t, sMask, sPrev, sChanged, sCross, sOv, sOi,
+                                                     Stamps<CC_RES_T>(l + 1, t));
         return;
     }
     const int nres = pb.helpers ? 2 * T : T;            // workgroups in front of the evaluators
     if ((int)blockIdx.x < nres) {
         const int t = (int)blockIdx.x - T;
         const int b = l - (t & 1);
-        if (b >= 0 && b < pb.nbat) ccpipe_cross_helper<D>(c, pb, b, t, sPrev
-#ifdef DLSM_PIPE_TIMING
-                                                           , l + 1
-#endif
-                                                           );
+        if (b >= 0 && b < pb.nbat) ccpipe_cross_helper<D>(c, pb, b, t, sPrev, Stamps<CC_RES_T>(l + 1, t));
         return;
     }
     __shared__ double sTab[EXPTAB_N];                   // 2^(j / 256): the evaluators' exponential
@@ -701,15 +669,11 @@ __global__ __launch_bounds__(CP_THREADS) void k_ccpipe_step(ChainView c, CcPipeB
         const bool odd = si >= nslE;
         if (k >= (odd ? nbO : nbE)) continue;                        // (a ragged last batch beside a full one)
         const int t = odd ? 2 * (si - nslE) + 1 : 2 * si;
-#ifdef DLSM_PIPE_TIMING
-        unsigned long long cts[2];
-        DLSM_CC_STAMP(0, (double)lane)
-#endif
+        Stamps<CC_ITEM_T> ist(l + 1, gw);
+        DLSM_STAMP(ist, 0, (double)lane)
         ccpipe_eval_item<D>(c, pb, odd ? beO : beE, t, k, lane, sWin[threadIdx.x >> 6], sTab);
-#ifdef DLSM_PIPE_TIMING
-        DLSM_CC_STAMP(1, (double)lane)
-        if (lane == 0 && l + 1 >= 0 && l + 1 < 32 && gw < 4096) { g_cc_item_t[l + 1][gw][0] = cts[0]; g_cc_item_t[l + 1][gw][1] = cts[1]; }
-#endif
+        DLSM_STAMP(ist, 1, (double)lane)
+        if (lane == 0) ist.flush();
     }
 }
 

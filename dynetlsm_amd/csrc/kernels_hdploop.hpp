@@ -21,6 +21,7 @@
 #pragma once
 #include "chain.hpp"
 #include "device_common.hpp"
+#include "kernel_stamps.hpp"
 #include "kernels_hdp.hpp"
 
 namespace dlsm {
@@ -109,14 +110,6 @@ __device__ inline double hdp_beta(const HdpRng &g, uint32_t kind, uint32_t idx, 
     const double gb = hdp_gamma(g, kind, 2 * idx + 1, b);
     return ga / (ga + gb);
 }
-
-#ifdef DLSM_PIPE_TIMING
-// phases of the globals' workgroup (stage 2's long pole), rows [4][phase]: profiles/hdp_tail_timing.py
-__device__ unsigned long long g_hdp_phase[16][2];
-#define DLSM_HDP_PHASE(I_) { __syncthreads(); if (threadIdx.x == 0) { unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)); g_hdp_phase[I_][0] = t_; g_hdp_phase[I_][1] = t_; } }
-#else
-#define DLSM_HDP_PHASE(I_)
-#endif
 
 // successes among n Bernoulli(p) trials; trial i = uniform i & 1 of attempt i >> 1
 __device__ inline int hdp_binomial(const HdpRng &g, uint32_t kind, uint32_t idx, int n, double p) {
@@ -339,7 +332,7 @@ __device__ __forceinline__ void hdp_globals_wg(const ChainView &c, const HdpLoop
     if (tid < 4) sTot[tid] = 0;
     if (tid == 0) sReady = 0;
     __syncthreads();
-    DLSM_HDP_PHASE(0)
+    stamp_workgroup_phase(0);      // (the globals' workgroup, stage 2's long pole)
     // every thread stages its share of the tables (one burst of loads); the wavefronts that sum the
     // columns wait for the shares on a counter in LDS, wavefront 3 goes on at once
     const int wfirst = wave < 3 && tid < (T - 1) * K ? hb.wover[tid] : 0;
@@ -404,7 +397,7 @@ __device__ __forceinline__ void hdp_globals_wg(const ChainView &c, const HdpLoop
         }
     }
     __syncthreads();
-    DLSM_HDP_PHASE(2)
+    stamp_workgroup_phase(2);      // (the globals' workgroup, stage 2's long pole)
     // global transition distribution beta ~ Dirichlet(gamma / K + m_bar) (hdp_lpcm.py:887)
     if (l3 >= 0 && l3 < K) {
         const double mb = (double)(sMsum[l3] - sWsum[l3]);
@@ -412,7 +405,7 @@ __device__ __forceinline__ void hdp_globals_wg(const ChainView &c, const HdpLoop
         sG[l3] = hdp_gamma_with(g, HK_BETA, (uint32_t)l3, hs->gamma / K + mb, gp);
     }
     __syncthreads();
-    DLSM_HDP_PHASE(3)
+    stamp_workgroup_phase(3);      // (the globals' workgroup, stage 2's long pole)
     double tot = 0.0;
     for (int k = 0; k < K; ++k) tot += sG[k];
     const double bnew = tid < K ? sG[tid] * (1.0 / tot) : 0.0;
@@ -429,7 +422,7 @@ __device__ __forceinline__ void hdp_globals_wg(const ChainView &c, const HdpLoop
         hs->mbar_total = mbt; hs->mbar_positive = mbp; hs->m00_total = m00;
         hs->m_rest_total = (double)sTot[1]; hs->override_total = (double)sTot[0];
     }
-    DLSM_HDP_PHASE(4)
+    stamp_workgroup_phase(4);      // (the globals' workgroup, stage 2's long pole)
 }
 
 // ---- transition distributions w[t, j, :] ~ Dirichlet(alpha beta + kappa e_j + n[t, j, :]) ---------
@@ -651,32 +644,6 @@ __device__ __forceinline__ void hdp_gam8_wg(const ChainView &c, const HdpLoopBuf
     hb.scr[HS_GAM8 + lane] = hdp_gamma(g, kind, idx, shape);
 }
 
-#ifdef DLSM_PIPE_TIMING
-// entry / exit stamps (100 MHz) of every workgroup of the six launches behind the label update
-// (profiles/hdp_tail_timing.py)
-__device__ unsigned long long g_hdp_t[6][512][2];
-struct HdpStamp {
-    int kid, blk;
-    __device__ HdpStamp(int kid_) : kid(kid_), blk((int)(blockIdx.x + gridDim.x * blockIdx.y)) {
-        if (threadIdx.x == 0 && blk < 512) {
-            unsigned long long t;
-            asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t));
-            g_hdp_t[kid][blk][0] = t;
-        }
-    }
-    __device__ ~HdpStamp() {
-        if (threadIdx.x == 0 && blk < 512) {
-            unsigned long long t;
-            asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t));
-            g_hdp_t[kid][blk][1] = t;
-        }
-    }
-};
-#define DLSM_HDP_STAMP(K_) HdpStamp hdp_stamp_(K_);
-#else
-#define DLSM_HDP_STAMP(K_)
-#endif
-
 // what is left for the launch of its own: the blending coefficient (needs the LAMBDA sums), the
 // three gamma variates whose shapes depend on the draws above, the new values
 // ... and the sample's trace rows (mu, sigma, beta, w are final by now; lambda and the six
@@ -685,7 +652,7 @@ struct HdpStamp {
 // (k_hdp_logp_batch_*), off the iteration's critical path.
 __device__ __forceinline__ void hdp_hypers_wg(const ChainView &c, const HdpLoopBuf &hb,
                                               HdpDeviceState *hs, const HdpTrace &tr, IterRef ir) {
-    DLSM_HDP_STAMP(3)
+    WorkgroupSpan span(3);     // (entry / exit stamps of launch 3 of the six behind the label update)
     __shared__ double sC[3], sLam, sEp[2];
     const int K = hb.K, T = c.T, D = c.D, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const HdpRng g = hdp_rng(c, ir.get());
@@ -877,7 +844,7 @@ __global__ __launch_bounds__(HDP_THREADS) void k_hdp_stage1(ChainView c, HdpLoop
                                                             int nrec, double *__restrict__ intercept,
                                                             double *__restrict__ trace_ic, IterRef ir,
                                                             uint8_t *__restrict__ trace_row) {
-    DLSM_HDP_STAMP(0)
+    WorkgroupSpan span(0);     // (entry / exit stamps of launch 0 of the six behind the label update)
     __builtin_amdgcn_s_setprio(3);          // ahead of the second queue's likelihood pass on a shared SIMD
     extern __shared__ int32_t sHist[];          // K K + K (the counts + tables role)
     const int K = hb.K, T = c.T;
@@ -926,7 +893,7 @@ __device__ __forceinline__ void hdp_fork_acquire_settled(const HdpFork &f) {
 template <int D>
 __global__ __launch_bounds__(HDP_THREADS) void k_hdp_stage2(ChainView c, HdpLoopBuf hb,
                                                             HdpDeviceState *hs, IterRef ir) {
-    DLSM_HDP_STAMP(1)
+    WorkgroupSpan span(1);     // (entry / exit stamps of launch 1 of the six behind the label update)
     __builtin_amdgcn_s_setprio(3);          // ahead of the second queue's likelihood pass on a shared SIMD
     const int K = hb.K;
     if (blockIdx.x == 0) { hdp_globals_wg(c, hb, hs, ir.get()); return; }
@@ -938,7 +905,7 @@ __global__ __launch_bounds__(HDP_THREADS) void k_hdp_stage2(ChainView c, HdpLoop
 template <int D>
 __global__ __launch_bounds__(HDP_THREADS) void k_hdp_stage3(ChainView c, HdpLoopBuf hb,
                                                             const HdpDeviceState *hs, IterRef ir) {
-    DLSM_HDP_STAMP(2)
+    WorkgroupSpan span(2);     // (entry / exit stamps of launch 2 of the six behind the label update)
     __builtin_amdgcn_s_setprio(3);          // ahead of the second queue's likelihood pass on a shared SIMD
     extern __shared__ double sGam[];            // K * K + K (the weights' role)
     const int K = hb.K, T = c.T;

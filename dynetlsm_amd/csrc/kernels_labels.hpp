@@ -5,6 +5,7 @@
 #pragma once
 #include "chain.hpp"
 #include "device_common.hpp"
+#include "kernel_stamps.hpp"
 
 namespace dlsm {
 
@@ -61,12 +62,7 @@ constexpr int LAB_WAVES = 8;
 
 __host__ __device__ inline int lab_row_pad(int K) { return K | 1; }
 
-#ifdef DLSM_PIPE_TIMING
-__device__ unsigned long long g_lab_t[4096][6];    // per wavefront: phase stamps (profiles/labels_phases.py)
-#define DLSM_LAB_STAMP(I_, DEP_) { unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "v"(DEP_)); lts[I_] = t_; }
-#else
-#define DLSM_LAB_STAMP(I_, DEP_)
-#endif
+// (phase stamps per wavefront, LAB_T: kernel_stamps.hpp; profiles/labels_phases.py reads them)
 template <int D, bool WLDS>
 __global__ __launch_bounds__(64 * LAB_WAVES) void k_sample_labels(
     ChainView c, const double *__restrict__ w, uint32_t iter,
@@ -76,10 +72,8 @@ __global__ __launch_bounds__(64 * LAB_WAVES) void k_sample_labels(
     const int KP = WLDS ? lab_row_pad(K) : K;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * LAB_WAVES + wave;
-#ifdef DLSM_PIPE_TIMING
-    unsigned long long lts[6] = {0, 0, 0, 0, 0, 0};
-#endif
-    DLSM_LAB_STAMP(0, (double)lane)
+    Stamps<LAB_T> lst(0, i);
+    DLSM_STAMP(lst, 0, (double)lane)
     const double *wt = w;                     // row (t, j) at wt + (t K + j) KP
     double *tables = smem;
     if (WLDS) {
@@ -90,7 +84,7 @@ __global__ __launch_bounds__(64 * LAB_WAVES) void k_sample_labels(
         wt = smem;
         tables = smem + (size_t)T * K * KP;
     }
-    DLSM_LAB_STAMP(1, (double)lane)
+    DLSM_STAMP(lst, 1, (double)lane)
     double *L = tables + (size_t)wave * 2 * T * K;
     double *pm = L + T * K;
     const bool live = i < N;                  // a whole wave is live or not
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(64 * LAB_WAVES) void k_sample_labels(
         }
     __syncthreads();
     if (!live) return;
-    DLSM_LAB_STAMP(2, (double)lane)
+    DLSM_STAMP(lst, 2, (double)lane)
     // the uniform of time t is drawn by lane t (T <= 64 per pass), all times at once
     double u_all = 0.0;
     // Lane k owns component k.  The sums over the components run in index order (as the
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(64 * LAB_WAVES) void k_sample_labels(
         bmk = s / tot;
     }
     if (lane < K) pm[lane] = L[lane] * bmk;
-    DLSM_LAB_STAMP(3, bmk)
+    DLSM_STAMP(lst, 3, bmk)
     __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): LDS writes landed
     __builtin_amdgcn_wave_barrier();
     // forward sampling :173-188: the cumulative sum runs in index order and lane k keeps its
@@ -165,10 +159,8 @@ __global__ __launch_bounds__(64 * LAB_WAVES) void k_sample_labels(
         if (lane == 0) z_out[(size_t)t * N + i] = zt;
         zprev = zt;
     }
-#ifdef DLSM_PIPE_TIMING
-    DLSM_LAB_STAMP(4, (double)zprev)
-    if (lane == 0 && i < 4096) for (int q = 0; q < 5; ++q) g_lab_t[i][q] = lts[q];
-#endif
+    DLSM_STAMP(lst, 4, (double)zprev)
+    if (lane == 0) lst.flush(0x1fu);
 }
 
 // ---- a12 on the f64 matrix cores: 16 nodes per workgroup ----
@@ -233,10 +225,8 @@ __global__ __launch_bounds__(LM_THREADS) void k_sample_labels_mfma(
     double *smu = sx + (size_t)T * NN * D;              // [K][D]
     const int tid = threadIdx.x, lane = tid & 63;
     const int node0 = blockIdx.x * NN;
-#ifdef DLSM_PIPE_TIMING
-    unsigned long long lts[6] = {0, 0, 0, 0, 0, 0};
-#endif
-    DLSM_LAB_STAMP(0, (double)lane)
+    Stamps<LAB_T> lst(0, (int)blockIdx.x);
+    DLSM_STAMP(lst, 0, (double)lane)
     // the transition matrices' first passes are requested before anything waits on a load
     constexpr int WPRE = 6;
     const int TKW = T * K * WS;
@@ -274,7 +264,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_sample_labels_mfma(
     }
     for (int q = tid; q < NN * S; q += LM_THREADS) Mb[q] = 1.0;     // the message of time T - 1
     __syncthreads();
-    DLSM_LAB_STAMP(1, (double)lane)
+    DLSM_STAMP(lst, 1, (double)lane)
     {
         const double lm = c.lmbda_p[0];
         for (int q = tid; q < T * NN * 4 * KS; q += LM_THREADS) {
@@ -301,7 +291,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_sample_labels_mfma(
     }
     __syncthreads();
     if (tid >= 64) return;                              // wavefront 0 carries on alone
-    DLSM_LAB_STAMP(2, (double)lane)
+    DLSM_STAMP(lst, 2, (double)lane)
     // backward messages (sample_labels.py:164-170)
     const int an = lane & 15, g = lane >> 4;            // A operand: node an % NN, component 4 s + g
     const int ar = an % NN;
@@ -377,7 +367,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_sample_labels_mfma(
 #pragma unroll
     for (int s = 0; s < KS; ++s)
         if (own) tab[(size_t)ar * S + g + 4 * s] *= Mb[ar * S + g + 4 * s];
-    DLSM_LAB_STAMP(3, (double)lane)
+    DLSM_STAMP(lst, 3, (double)lane)
     __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): LDS writes landed
     __builtin_amdgcn_wave_barrier();
     // forward sampling (:173-188): four lanes per node, KS components each
@@ -417,10 +407,8 @@ __global__ __launch_bounds__(LM_THREADS) void k_sample_labels_mfma(
         if (q == 0 && fl < NN && node < N) z_out[(size_t)t * N + node] = zt;
         zprev = zt;
     }
-#ifdef DLSM_PIPE_TIMING
-    DLSM_LAB_STAMP(4, (double)zprev)
-    if (lane == 0 && blockIdx.x < 4096) for (int qq = 0; qq < 5; ++qq) g_lab_t[blockIdx.x][qq] = lts[qq];
-#endif
+    DLSM_STAMP(lst, 4, (double)zprev)
+    if (lane == 0) lst.flush(0x1fu);
 }
 
 // The counts the conjugate updates need (sample_labels.py:176-188): n[0][0][k] initial labels,

@@ -2,6 +2,7 @@
 #pragma once
 #include "chain.hpp"
 #include "device_common.hpp"
+#include "kernel_stamps.hpp"
 
 namespace dlsm {
 
@@ -122,9 +123,6 @@ constexpr int LLU_THREADS = 128;
 constexpr int LLU_ROWS = LLU_ROWS_V;
 constexpr int LLU_SPLIT = 128 / LLU_ROWS;         // workgroups per tile
 
-#ifdef DLSM_PIPE_TIMING
-__device__ unsigned long long g_ll_t[8192][3];     // per wavefront: entry, exit (100 MHz), HW_ID
-#endif
 // workgroups of the undirected pass per time step: two (row halves) per tile above the diagonal, ONE per
 // diagonal tile (below) - nt (nt - 1) + nt = nt^2
 __host__ __device__ inline int llu_blocks_per_slice(int nt) { return nt * nt; }
@@ -144,11 +142,10 @@ __global__ __launch_bounds__(LLU_THREADS) __attribute__((amdgpu_waves_per_eu(D <
     __shared__ __attribute__((aligned(16))) double sTab[EXPTAB_N];      // tab_exp (device_common.hpp)
     const int tid = threadIdx.x;
     const int N = c.N;
-#ifdef DLSM_PIPE_TIMING
-    unsigned long long tl0;
-    unsigned int hwid, xccid;
-    asm volatile("s_memrealtime %0\n\ts_getreg_b32 %1, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %2, hwreg(HW_REG_XCC_ID)\n\ts_waitcnt lgkmcnt(0)" : "=s"(tl0), "=s"(hwid), "=s"(xccid));
-#endif
+    // stamps per wavefront (LL_T, profiles/loglik_timing.py): 0 entry, 1 exit, 2 where it ran
+    Stamps<LL_T> lst(0, (int)blockIdx.x * 2 + (tid >> 6));
+    DLSM_STAMP(lst, 0, tid)
+    lst.mark_place(2);
     static_assert(2 * LLU_THREADS == EXPTAB_N, "two table entries per thread");
     sTab[tid] = c_exp2_tab[tid];                   // visible after the staging barrier below
     sTab[tid + LLU_THREADS] = c_exp2_tab[tid + LLU_THREADS];
@@ -351,14 +348,8 @@ __global__ __launch_bounds__(LLU_THREADS) __attribute__((amdgpu_waves_per_eu(D <
     __syncthreads();
     if (tid < 2 + M)
         partials[(size_t)blockIdx.x * (2 + M) + tid] = sRed[tid] + sRed[(2 + M) + tid];
-#ifdef DLSM_PIPE_TIMING
-    {
-        unsigned long long tl1;
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tl1) : "v"(acc[1]));
-        const unsigned w = blockIdx.x * 2 + (tid >> 6);
-        if ((tid & 63) == 0 && w < 8192) { g_ll_t[w][0] = tl0; g_ll_t[w][1] = tl1; g_ll_t[w][2] = (unsigned long long)hwid | ((unsigned long long)xccid << 32); }
-    }
-#endif
+    DLSM_STAMP(lst, 1, acc[1])
+    if ((tid & 63) == 0) lst.flush();
 }
 
 template <int D, int M>

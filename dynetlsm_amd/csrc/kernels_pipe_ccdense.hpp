@@ -114,17 +114,11 @@ template <int D, int G>
 __device__ __forceinline__ void pipe_resolve(const ChainView &c, const PipeBuf &pb, int b, int t,
                                              double *sH, double *sPart,
                                              unsigned long long (*sMask)[2], int *sPrev,
-                                             unsigned char *sSat, int *sOwn, bool own_prev
-#ifdef DLSM_PIPE_TIMING
-                                             , int tl
-#endif
-                                             ) {
+                                             unsigned char *sSat, int *sOwn, bool own_prev,
+                                             Stamps<PIPE_RES_T> rst) {
     constexpr int PW = 2 * D + 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef DLSM_PIPE_TIMING
-    unsigned long long ts[5] = {0, 0, 0, 0, 0};
-#endif
-    DLSM_STAMP(0, (double)tid)
+    DLSM_STAMP(rst, 0, (double)tid)
     const int N = c.N;
     const int j0 = b * PP_B;
     const int nb = min(PP_B, N - j0);
@@ -208,7 +202,7 @@ __device__ __forceinline__ void pipe_resolve(const ChainView &c, const PipeBuf &
     for (int u = 0; u < 8; ++u)
         ((double2 *)sH)[min(u * PP_THREADS + tid, nb * (PP_B / 2) - 1)] = blk[u];
     __syncthreads();                                   // sPrev, sH visible
-    DLSM_STAMP(1, (double)tid)
+    DLSM_STAMP(rst, 1, (double)tid)
     const bool satk = sSat[k] != 0;                    // column k is resolved in the log domain
     const bool anysat = __ballot(satk) != 0ull;        // (practically never: wave-uniform slow path)
     if (nprev > 0) {
@@ -251,7 +245,7 @@ __device__ __forceinline__ void pipe_resolve(const ChainView &c, const PipeBuf &
         if (lane == 0) sMask[0][half] = g;
     }
     __syncthreads();
-    DLSM_STAMP(2, (double)tid)
+    DLSM_STAMP(rst, 2, (double)tid)
     int cur = 0;
     for (int pass = 0; pass < 2 * PP_B + 2; ++pass) {
         const unsigned long long gm = sMask[cur][part >> 2];
@@ -298,7 +292,7 @@ __device__ __forceinline__ void pipe_resolve(const ChainView &c, const PipeBuf &
         cur ^= 1;
         if (same) break;
     }
-    DLSM_STAMP(3, (double)cur)
+    DLSM_STAMP(rst, 3, (double)cur)
     if (owner) {
         const unsigned long long m0 = sMask[cur][0], m1 = sMask[cur][1];
         const unsigned long long mine = half == 0 ? m0 : m1;
@@ -326,10 +320,7 @@ __device__ __forceinline__ void pipe_resolve(const ChainView &c, const PipeBuf &
             sOwn[0] = cnt;
         }
     }
-#ifdef DLSM_PIPE_TIMING
-    DLSM_STAMP(4, (double)cur)
-    if (tid == 0 && tl >= 0 && tl < 24 && t < 32)
-        for (int i = 0; i < 5; ++i) g_pipe_res_t[tl][t][i] = ts[i];
-#endif
+    DLSM_STAMP(rst, 4, (double)cur)
+    if (tid == 0) rst.flush();
 }
 

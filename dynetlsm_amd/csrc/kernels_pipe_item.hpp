@@ -91,11 +91,8 @@ __device__ __forceinline__ void pipe_h_operands(const ChainView &c, const double
 // 32-bit offsets from a scalar base.
 template <int D, int MODEL, int G, bool SQ>
 __device__ __forceinline__ void pipe_h_entry(const ChainView &c, const PipeBuf &pb, int be, int nb, int t,
-                                             const double *etab, int kk, int e, const PipeHPre<D> &o, bool stamp
-#ifdef DLSM_PIPE_TIMING
-                                             , unsigned long long *ts
-#endif
-                                             ) {
+                                             const double *etab, int kk, int e, const PipeHPre<D> &o,
+                                             Stamps<PIPE_ITEM_T> &st) {
     const int j0 = be * PP_B;
     const int jprev = pipe_window_start(be, G) * PP_B;
     const int ncross = j0 - jprev;
@@ -120,9 +117,7 @@ __device__ __forceinline__ void pipe_h_entry(const ChainView &c, const PipeBuf &
     const double a1 = dist_fast<D>(xm0, xa1, SQ ? 1 : 0);
     const double b0 = dist_fast<D>(xm1, xa0, SQ ? 1 : 0);
     const double b1 = dist_fast<D>(xm1, xa1, SQ ? 1 : 0);
-#ifdef DLSM_PIPE_TIMING
-    if (stamp) { DLSM_STAMP(4, a0 + b1) }
-#endif
+    if (st.armed()) { DLSM_STAMP(st, 4, a0 + b1) }          // "H operands here": the lane's first entry
     double h;
     if (MODEL == DLSM_UNDIRECTED) {
         const double eb0 = SQ ? tab_exp11_clamped(-b0, etab) : tab_exp11(-b0, etab);
@@ -167,11 +162,8 @@ __device__ __forceinline__ void pipe_h_entry(const ChainView &c, const PipeBuf &
 template <int D, int MODEL, int G>
 __device__ __forceinline__ void pipe_item_finish(const ChainView &c, const PipeBuf &pb, int be, int nb,
                                                  int t, int k, int p, int lane, const double *etab,
-                                                 double acc, RatioAcc &ra, bool noflush
-#ifdef DLSM_PIPE_TIMING
-                                                 , unsigned long long *ts
-#endif
-                                                 ) {
+                                                 double acc, RatioAcc &ra, bool noflush,
+                                                 Stamps<PIPE_ITEM_T> &st) {
     constexpr int PW = 2 * D + 2;
     const int N = c.N, W = c.W;
     const int j0 = be * PP_B;
@@ -194,19 +186,14 @@ __device__ __forceinline__ void pipe_item_finish(const ChainView &c, const PipeB
         double2 *f = (double2 *)pb.full0 + (((size_t)bb * c.T + t) * PP_B + k) * pb.parts + p;
         coh_store2<false>(f, 0u, make_double2(tot_l, tot_r));
     }
-    DLSM_STAMP(3, tot_r)
+    DLSM_STAMP(st, 3, tot_r)
     // this lane's H entries (pipe_h_decode).  Rows of `props` and the bits are addressed as
     // 32-bit offsets from scalar bases.
     const char *yrows = (const char *)(c.ybits + (size_t)t * N * W);
     const char *ytrows = MODEL == DLSM_DIRECTED ? (const char *)(c.ytbits + (size_t)t * N * W) : nullptr;
     int f = hf0;
 #define DLSM_H_CALL(SQ_, KK_, E_, O_, STAMP_)                                                         \
-    pipe_h_entry<D, MODEL, G, SQ_>(c, pb, be, nb, t, etab, KK_, E_, O_, STAMP_ DLSM_H_TS)
-#ifdef DLSM_PIPE_TIMING
-#define DLSM_H_TS , ts
-#else
-#define DLSM_H_TS
-#endif
+    (st.arm(STAMP_), pipe_h_entry<D, MODEL, G, SQ_>(c, pb, be, nb, t, etab, KK_, E_, O_, st))
     // HSHIFT (the launch-per-batch evaluators: a workgroup's 16 wavefronts hold items k0 .. k0 + 15 of one
     // part, wavefronts w, w + 4, w + 8, w + 12 share a SIMD): the LAST wavefront of a SIMD hands its
     // first-round entries to the FIRST one - the same arithmetic on the same SIMD, but no longer the launch's tail
@@ -234,8 +221,7 @@ __device__ __forceinline__ void pipe_item_finish(const ChainView &c, const PipeB
         first = false;
     }
 #undef DLSM_H_CALL
-#undef DLSM_H_TS
-    DLSM_STAMP(5, acc)
+    DLSM_STAMP(st, 5, acc)
 }
 
 // What an item reads about its OWN node before the first neighbour: static for the whole sweep
@@ -291,17 +277,11 @@ __host__ __device__ constexpr int pipe_prefetch_trips(int D) {
 template <int D, int MODEL, bool TP, int G>
 __device__ __forceinline__ void pipe_eval_item(const ChainView &c, const PipeBuf &pb, int be,
                                                int nb, int t, int k, int p, int lane,
-                                               const double *etab, const PipeItemPre<D> &pre
-#ifdef DLSM_PIPE_TIMING
-                                               , int tl, int tgw
-#endif
-                                               ) {
+                                               const double *etab, const PipeItemPre<D> &pre,
+                                               Stamps<PIPE_ITEM_T> st) {
     constexpr int PW = 2 * D + 2;
     const int N = c.N, W = c.W;
-#ifdef DLSM_PIPE_TIMING
-    unsigned long long ts[6] = {0, 0, 0, 0, 0, 0};
-#endif
-    DLSM_STAMP(0, (double)lane)
+    DLSM_STAMP(st, 0, (double)lane)
     const int j0 = be * PP_B, jk = j0 + k;
     const int jprev = pipe_window_start(be, G) * PP_B;      // nodes >= jprev: snapshot positions
     const int ncross = j0 - jprev;
@@ -411,8 +391,8 @@ __device__ __forceinline__ void pipe_eval_item(const ChainView &c, const PipeBuf
         DLSM_PIPE_MASKS(u)                                                                    \
         if (__builtin_amdgcn_inverse_ballot_w64(vm_))                                         \
             DLSM_PIPE_TERM(xpre[u], yb_, ycb_, rpre[MODEL == DLSM_DIRECTED ? u : 0], FLUSH_, SQ_) \
-        if (u == 0) { DLSM_STAMP(1, ra.P0) }                                                  \
-        if (u == PP_NPRE - 1) { DLSM_STAMP(2, ra.P0) }                                        \
+        if (u == 0) { DLSM_STAMP(st, 1, ra.P0) }                                              \
+        if (u == PP_NPRE - 1) { DLSM_STAMP(st, 2, ra.P0) }                                    \
     }                                                                                         \
     /* the trips beyond the prefetched ones.  TP: each trip requests the next one's operands   \
        (clamped address, no predication) before it computes. */                               \
@@ -445,15 +425,8 @@ __device__ __forceinline__ void pipe_eval_item(const ChainView &c, const PipeBuf
 #undef DLSM_PIPE_REQUEST
 #undef DLSM_PIPE_MASKS
 #undef DLSM_PIPE_TERM
-    pipe_item_finish<D, MODEL, G>(c, pb, be, nb, t, k, p, lane, etab, acc, ra, noflush
-#ifdef DLSM_PIPE_TIMING
-                                       , ts
-#endif
-                                       );
-#ifdef DLSM_PIPE_TIMING
-    if (lane == 0 && tl >= 0 && tl < 24 && tgw < 4096)
-        for (int i = 0; i < 6; ++i) g_pipe_item_t[tl][tgw][i] = ts[i];
-#endif
+    pipe_item_finish<D, MODEL, G>(c, pb, be, nb, t, k, p, lane, etab, acc, ra, noflush, st);
+    if (lane == 0) st.flush();
 }
 
 

@@ -94,11 +94,7 @@ __device__ __forceinline__ void pipe_lds_trips(int nw64, int P, const PipePlan &
                                                const double (&xk1)[D], double E, int nflush,
                                                const unsigned long long *yrow, unsigned long long ym,
                                                const double *etab, const double *sX, const double *sM, double *hrow,
-                                               RatioAcc &ra
-#ifdef DLSM_PIPE_TIMING
-                                               , unsigned long long *ts
-#endif
-                                               ) {
+                                               RatioAcc &ra, Stamps<PIPE_ITEM_T> &st) {
     const int ntp = pl.trips();
     // (nw64: 8-byte words of a row of the network)
     const double *row = sX + lane * D;                      // this lane's neighbour of trip 0, 1, ..: stride 64 D
@@ -151,7 +147,7 @@ __device__ __forceinline__ void pipe_lds_trips(int nw64, int P, const PipePlan &
                 }
             }
         }
-        if (u == 0) { DLSM_STAMP(1, ra.P0) }
+        if (u == 0) { DLSM_STAMP(st, 1, ra.P0) }
 #pragma unroll
         for (int d = 0; d < D; ++d) xi[d] = xn[d];
         ym = ymn; g = gn;
@@ -187,7 +183,7 @@ __device__ __forceinline__ void pipe_lds_trips(int nw64, int P, const PipePlan &
         {
             DLSM_LDS_TERM()
         }
-        if (pl.w == 0 && i == 0) { DLSM_STAMP(1, ra.P0) }
+        if (pl.w == 0 && i == 0) { DLSM_STAMP(st, 1, ra.P0) }
         DLSM_LDS_PRIO_STEP()
         g = gb;
         DLSM_LDS_NEXT(g)
@@ -204,13 +200,13 @@ __device__ __forceinline__ void pipe_lds_trips(int nw64, int P, const PipePlan &
     }
     if (i < pl.r) {
         DLSM_LDS_TERM()
-        if (pl.w == 0 && i == 0) { DLSM_STAMP(1, ra.P0) }
+        if (pl.w == 0 && i == 0) { DLSM_STAMP(st, 1, ra.P0) }
     }
 #undef DLSM_LDS_NEXT
 #undef DLSM_LDS_PRIO_STEP
 #undef DLSM_LDS_TERM
 #undef DLSM_LDS_LIN
-    DLSM_STAMP(2, ra.P0)
+    DLSM_STAMP(st, 2, ra.P0)
 }
 
 // ---- the resolvers' cross products, by the evaluators ------------------------------------------------------
@@ -261,17 +257,10 @@ __device__ __forceinline__ void pipe_xserve_finish(const PipeXServe &xs, int lan
     if (lane == 0) __hip_atomic_store(xs.slot, prod, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-#ifdef DLSM_PIPE_TIMING
-#define DLSM_LDS_TS , ts
-#else
-#define DLSM_LDS_TS
-#endif
+// (entry: the stamp record whose slot 0 holds the wavefront's first instruction in the kernel)
 template <int D>
-__device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf &pb, int l, double *lds
-#ifdef DLSM_PIPE_TIMING
-                                              , unsigned long long t_kernel
-#endif
-                                              ) {
+__device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf &pb, int l, double *lds,
+                                              const Stamps<PIPE_ITEM_T> &entry) {
     constexpr int PW = 2 * D + 2;
     // the launch's arguments in one piece (PipeLds): the pointers and scalars below are 128 contiguous bytes of the
     // kernel's argument block, pinned here so that they are requested together by the first instructions
@@ -316,12 +305,10 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
         const int t = odd ? 2 * (si - nslE) + 1 : 2 * si;
         const int k = k0 + wave;
         const bool live = k < nb;
-#ifdef DLSM_PIPE_TIMING
         // stamps (profiles/pipe_timing.py): 0 entry, 4 rows + table staged (behind the barrier), 1 first trip done,
         // 2 last trip done, 3 = 5 record stored
-        unsigned long long ts[6] = {0, 0, 0, 0, 0, 0};
-#endif
-        DLSM_STAMP(0, (double)lane)
+        Stamps<PIPE_ITEM_T> st(l + 1, wg * PP_WAVES + wave);
+        DLSM_STAMP(st, 0, (double)lane)
         const int j0 = be * PP_B, jk = j0 + min(k, nb - 1);
         const int jprev = max(j0 - PP_B, 0);                             // nodes >= jprev: snapshot positions
         // (T N < 2^31: node indices in 32 bits, one 64-bit product per base)
@@ -380,16 +367,12 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
         // (a part without trips - more parts than trips at tiny N - names a trip behind the row: clamped, unused)
         const unsigned long long ym0 = scalar_load_u64(yrow + min(pl.trip(0, p, P), (a.W >> 1) - 1));
         double *hrow = a.Hd + (size_t)((uint32_t)(((be & 1) * T + t) * PP_B + min(k, nb - 1)) * (uint32_t)(2 * PP_B));     // (< 2^31 doubles: T < 128)
-#if defined(DLSM_PIPE_TIMING) && DLSM_PIPE_TIMING == 2      // (prologue probe: slot 1 = requests issued, slot 2 = at the barrier)
-        DLSM_STAMP(1, (double)lane)
-#endif
+        if (STAMP_PROLOGUE_PROBE) { DLSM_STAMP(st, 1, (double)lane) }     // (the probe: slot 1 = requests issued, slot 2 = at the barrier)
         if (first) ((double2 *)sTab)[tid] = tabv;
         if (s < nst) stage_store(s);
         for (s += PP_WAVES; s < nst; s += PP_WAVES) { stage_request(s); stage_store(s); }
-#if defined(DLSM_PIPE_TIMING) && DLSM_PIPE_TIMING == 2
-        DLSM_STAMP(2, xk0[0])
-        unsigned long long ts1 = ts[1], ts2 = ts[2];
-#endif
+        if (STAMP_PROLOGUE_PROBE) { DLSM_STAMP(st, 2, xk0[0]) }
+        const unsigned long long probe1 = st.get(1), probe2 = st.get(2);    // (the trips stamp these slots again)
         __syncthreads();
         // The whole of it behind the barrier: in front of it the four wavefronts of a SIMD issue their prologues
         // one after the other and every instruction of a serving wavefront keeps the workgroup's other fifteen
@@ -397,13 +380,13 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
         // trip costs nothing - the SIMD's other three have trips to issue.
         pipe_xserve_request(a, l, wg, wave, lane, xs);
         pipe_xserve_finish(xs, lane);
-        DLSM_STAMP(4, xk0[0])
+        DLSM_STAMP(st, 4, xk0[0])
         if (live) {
             RatioAcc ra;
             const bool noflush = nflush >= 64 * ntp && !a.squared;
-            if (noflush) pipe_lds_trips<D, false, false>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, ra DLSM_LDS_TS);
-            else if (a.squared) pipe_lds_trips<D, true, true>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, ra DLSM_LDS_TS);
-            else pipe_lds_trips<D, true, false>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, ra DLSM_LDS_TS);
+            if (noflush) pipe_lds_trips<D, false, false>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, ra, st);
+            else if (a.squared) pipe_lds_trips<D, true, true>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, ra, st);
+            else pipe_lds_trips<D, true, false>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, ra, st);
             double tot_l, tot_r;
             if (noflush) {
                 // the products of the whole wave stay in range: multiply across lanes
@@ -415,17 +398,11 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
                 double2 *f = (double2 *)a.full0 + (uint32_t)((((be & 1) * T + t) * PP_B + k) * P + p);
                 *f = make_double2(tot_l, tot_r);
             }
-#ifdef DLSM_PIPE_TIMING
-            DLSM_STAMP(3, tot_r)
-            ts[5] = ts[3];
-#if DLSM_PIPE_TIMING == 2
-            ts[1] = ts1; ts[2] = ts2;
-#endif
-            ts[0] = t_kernel;           // (the round's entry stamp gives way to the wavefront's first stamp in the kernel)
-            const int tgw = wg * PP_WAVES + wave;
-            if (lane == 0 && l + 1 >= 0 && l + 1 < 24 && tgw < 4096)
-                for (int i = 0; i < 6; ++i) g_pipe_item_t[l + 1][tgw][i] = ts[i];
-#endif
+            DLSM_STAMP(st, 3, tot_r)
+            st.set(5, st.get(3));
+            if (STAMP_PROLOGUE_PROBE) { st.set(1, probe1); st.set(2, probe2); }
+            st.set(0, entry.get(0));    // (the round's entry stamp gives way to the wavefront's first stamp in the kernel)
+            if (lane == 0) st.flush();
         }
     }
 }

@@ -38,6 +38,7 @@
 // saturate - is resolved in the log domain, with the logs of its H factors: pipe_resolve.)
 #pragma once
 #include "kernels_spec_sweep.hpp"
+#include "kernel_stamps.hpp"
 
 namespace dlsm {
 
@@ -215,20 +216,8 @@ __global__ __launch_bounds__(256) void k_pipe_propose(ChainView c, PipeBuf pb, I
     pipe_propose_rows<D>(c, nb, ir.get(), fb, (int)threadIdx.x);
 }
 
-#ifdef DLSM_PIPE_TIMING
-// phase stamps (100 MHz constant clock) of every evaluator wavefront and every resolver
-// workgroup of the last sweep: profiles/pipe_timing.py reads them
-__device__ unsigned long long g_pipe_item_t[24][4096][6];
-__device__ unsigned long long g_pipe_res_t[24][32][5];
-__device__ __forceinline__ unsigned long long pipe_clock(double dep) {
-    unsigned long long t;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "v"(dep));
-    return t;
-}
-#define DLSM_STAMP(I_, DEP_) ts[I_] = pipe_clock(DEP_);
-#else
-#define DLSM_STAMP(I_, DEP_)
-#endif
+// (phase stamps of every evaluator wavefront - PIPE_ITEM_T - and every resolver workgroup - PIPE_RES_T - of the last
+// sweep: kernel_stamps.hpp; profiles/pipe_timing.py reads them)
 
 // ---- the item's wavefront reductions -------------------------------------------------------
 // An evaluator launch is bound by float64 VALU issue (profiles/pipe_timing.py: the four
@@ -296,17 +285,11 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
                                                 double *sD, double *sPart,
                                                 unsigned long long (*sMask)[2],
                                                 double *sCross,
-                                                unsigned long long *sSatMask, double *sTab, bool served
-#ifdef DLSM_PIPE_TIMING
-                                                , int tl
-#endif
-                                                ) {
+                                                unsigned long long *sSatMask, double *sTab, bool served,
+                                                Stamps<PIPE_RES_T> rst) {
     constexpr int PW = 2 * D + 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef DLSM_PIPE_TIMING
-    unsigned long long ts[5] = {0, 0, 0, 0, 0};
-#endif
-    DLSM_STAMP(0, (double)tid)
+    DLSM_STAMP(rst, 0, (double)tid)
     const int N = c.N;
     const int j0 = b * PP_B;
     const int nb = min(PP_B, N - j0);
@@ -451,7 +434,7 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
     // (the table exponential: the compiler's exp() keeps a dozen float64 constants alive through
     // the whole batch loop, in registers the blocks above need - it spilled them)
     if (owner && !sat) r *= tab_exp(lr, sTab);
-    DLSM_STAMP(1, (double)tid)
+    DLSM_STAMP(rst, 1, (double)tid)
     const unsigned long long sat0 = sSatMask[0], sat1 = sSatMask[1];
     const bool anysat = (sat0 | sat1) != 0ull;         // workgroup-uniform; practically never
     const bool satk = (((half ? sat1 : sat0) >> lane) & 1ull) != 0ull;
@@ -502,7 +485,7 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
         if (lane == 0) sMask[0][half] = g;
     }
     __syncthreads();
-    DLSM_STAMP(2, (double)tid)
+    DLSM_STAMP(rst, 2, (double)tid)
     int cur = 0;
     for (int pass = 0; pass < 2 * PP_B + 2; ++pass) {
         const unsigned long long gm = sMask[cur][part >> 2];
@@ -549,7 +532,7 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
         cur ^= 1;
         if (same) break;
     }
-    DLSM_STAMP(3, (double)cur)
+    DLSM_STAMP(rst, 3, (double)cur)
     if (owner) {
         const unsigned long long m0 = sMask[cur][0], m1 = sMask[cur][1];
         const unsigned long long mine = half == 0 ? m0 : m1;
@@ -569,11 +552,8 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
             pmw[0] = m0; pmw[1] = m1;
         }
     }
-#ifdef DLSM_PIPE_TIMING
-    DLSM_STAMP(4, (double)cur)
-    if (tid == 0 && tl >= 0 && tl < 24 && t < 32)
-        for (int i = 0; i < 5; ++i) g_pipe_res_t[tl][t][i] = ts[i];
-#endif
+    DLSM_STAMP(rst, 4, (double)cur)
+    if (tid == 0) rst.flush();
 }
 
 }  // namespace dlsm
@@ -603,14 +583,9 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
     const bool grid3 = MODEL_ == DLSM_UNDIRECTED && G == 1 && pb.lds_eval && (int)gridDim.x > T;    // kernels_pipe_lds.hpp's evaluators
     if (grid3) {
         if (bx >= T) {
-#ifdef DLSM_PIPE_TIMING
-            const unsigned long long t_kernel = pipe_clock((double)threadIdx.x);    // the wavefront's first instruction
-#endif
-            pipe_eval_lds<D>(c, pb, l, pp_sH
-#ifdef DLSM_PIPE_TIMING
-                             , t_kernel
-#endif
-                             );
+            Stamps<PIPE_ITEM_T> first;                  // (read by the item's record, never flushed itself)
+            DLSM_STAMP(first, 0, (double)threadIdx.x)               // the wavefront's first instruction
+            pipe_eval_lds<D>(c, pb, l, pp_sH, first);
             return;
         }
     }
@@ -625,11 +600,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
             if (l == -1 && threadIdx.x < PP_B)                            // the sweep's first launch: every slot empty
                 pb.xprod[(size_t)t * PP_B + threadIdx.x] = __longlong_as_double((long long)PP_XP_EMPTY);
             if (b < 0 || b >= pb.nbat) return;
-            row_resolve<D>(c, pb, b, t, pp_sH, sPart, sMask, sCross, sSatMask, sTab, served
-#ifdef DLSM_PIPE_TIMING
-                                  , l + 1
-#endif
-                                  );
+            row_resolve<D>(c, pb, b, t, pp_sH, sPart, sMask, sCross, sSatMask, sTab, served, Stamps<PIPE_RES_T>(l + 1, t));
             return;
         }
         bool own_prev = false;
@@ -637,11 +608,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
             const int b = G * (l - (t & 1)) + g;
             if (b < 0 || b >= pb.nbat) continue;
             if (own_prev) __syncthreads();          // the LDS of the batch before is free again
-            pipe_resolve<D, G>(c, pb, b, t, pp_sH, sPart, sMask, sPrev, sSat, sOwn, own_prev
-#ifdef DLSM_PIPE_TIMING
-                            , l + 1
-#endif
-                            );
+            pipe_resolve<D, G>(c, pb, b, t, pp_sH, sPart, sMask, sPrev, sSat, sOwn, own_prev, Stamps<PIPE_RES_T>(l + 1, t));
             own_prev = true;
         }
         return;
@@ -650,9 +617,8 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
     // the items need a second round the host launches the PIPE_UNDIRECTED_LONG instantiation, whose evaluators are
     // pipe_eval_item's software-pipelined trips below)
     if (MODEL_ == DLSM_UNDIRECTED) return;
-#ifdef DLSM_PIPE_TIMING
-    const unsigned long long t_kernel = pipe_clock((double)threadIdx.x);    // the wavefront's first instruction
-#endif
+    Stamps<PIPE_ITEM_T> first;                  // (read by the item's record, never flushed itself)
+    DLSM_STAMP(first, 0, (double)threadIdx.x)                       // the wavefront's first instruction
     const int lane = threadIdx.x & 63;
     const int nE = (T + 1) / 2, nO = T / 2;
     const int beE = G * (l + 1), beO = G * l;        // first batch evaluated (even / odd slices)
@@ -715,16 +681,12 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
         constexpr int IM = MODEL == DLSM_DIRECTED_CASE_CONTROL ? DLSM_DIRECTED : MODEL;
         PipeItemPre<D> pre;
         pipe_item_prologue<D, IM>(c, pb, be, t, k, p, lane, pre);
-        pipe_eval_item<D, IM, TP, G>(c, pb, be, nb, t, k, p, lane, pp_sH, pre
-#ifdef DLSM_PIPE_TIMING
-            , l + 1, gw
-#endif
-            );
-#ifdef DLSM_PIPE_TIMING
+        pipe_eval_item<D, IM, TP, G>(c, pb, be, nb, t, k, p, lane, pp_sH, pre, Stamps<PIPE_ITEM_T>(l + 1, gw));
         // (slot 4, "H operands here", gives way to the wavefront's first stamp in the kernel: both evaluators
         // on one time axis)
-        if (lane == 0 && l + 1 >= 0 && l + 1 < 24 && q < 4096) g_pipe_item_t[l + 1][q][4] = t_kernel;
-#endif
+        Stamps<PIPE_ITEM_T> item(l + 1, q);
+        item.set(4, first.get(0));
+        if (lane == 0) item.flush(1u << 4);
     }
 }
 
@@ -757,11 +719,7 @@ __device__ __forceinline__ void pipe_last_ride_wg(const ChainView &c, const Pipe
             __shared__ double sCross[PP_B];
             __shared__ unsigned long long sSatMask[2];
             __shared__ double sTab[EXPTAB_N];
-            row_resolve<D>(c, pb, b, t, pp_sH, sPart, sMask, sCross, sSatMask, sTab, false
-#ifdef DLSM_PIPE_TIMING
-                                  , l + 1
-#endif
-                                  );
+            row_resolve<D>(c, pb, b, t, pp_sH, sPart, sMask, sCross, sSatMask, sTab, false, Stamps<PIPE_RES_T>(l + 1, t));
         }
         __syncthreads();                    // the accepted positions of this workgroup are in memory
         double acc[W];

@@ -4,7 +4,6 @@ resolver workgroups (stamps 0 entry, 2 state and lists loaded + cross sums hande
 -DDLSM_PIPE_TIMING.
     python profiles/ccpipe_timing.py tmp_timing/libtiming.so [out.json]
 """
-import ctypes as C
 import json
 import os
 import sys
@@ -18,6 +17,7 @@ from dynetlsm_amd import _lib  # noqa: E402
 _lib.LIB_PATH = os.path.abspath(sys.argv[1])
 from dynetlsm_amd import Chain, SamplerGrid  # noqa: E402
 from dynetlsm_amd.synthetic import synthetic_sparse_directed  # noqa: E402
+from stamps import read_stamps  # noqa: E402  (profiles/stamps.py)
 
 T, N, Cn = 5, 10000, 100
 X, radii, degree, in_edges, out_edges = synthetic_sparse_directed(T, N, 20, 0)
@@ -33,11 +33,8 @@ ch.trace_alloc(64, logp0=0.0)
 ch.lsm_run(1, 30, procrustes_ref=0)
 ch.synchronize()
 L = _lib.load()
-res = np.zeros((32, 16, 8), dtype=np.uint64)
-items = np.zeros((32, 4096, 2), dtype=np.uint64)
-L.dlsm_debug_ccpipe_timing.restype = C.c_int
-L.dlsm_debug_ccpipe_timing.argtypes = [C.c_void_p, C.c_void_p]
-assert L.dlsm_debug_ccpipe_timing(res.ctypes.data, items.ctypes.data) == 0
+res = read_stamps(L, 'cc_res_t', (32, 16, 8))
+items = read_stamps(L, 'cc_item_t', (32, 4096, 2))
 out = []
 for l in range(32):
     r = res[l].astype(np.int64); it = items[l].astype(np.int64)

@@ -3,7 +3,6 @@ device-resident HDP-LPCM iteration (stage 1-3, hypers, logp sums, finalize) at c
 role of a multi-role launch is its long pole (engine built with -DDLSM_PIPE_TIMING).
     python profiles/hdp_tail_timing.py tmp_timing/libtiming.so [out.json]
 """
-import ctypes as C
 import json
 import os
 import sys
@@ -17,6 +16,7 @@ from dynetlsm_amd import _lib  # noqa: E402
 _lib.LIB_PATH = os.path.abspath(sys.argv[1])
 from dynetlsm_amd import DynamicNetworkHDPLPCM  # noqa: E402
 from dynetlsm_amd.synthetic import synthetic_hdp_network  # noqa: E402
+from stamps import read_stamps  # noqa: E402  (profiles/stamps.py)
 
 T, N, D, K = 10, 2000, 2, 20
 net = synthetic_hdp_network(T=T, N=N, D=D, density=0.03, seed=0)
@@ -30,10 +30,7 @@ m._prepare(net['Y'], init=dict(X=net['X_init'], intercept=[net['intercept']], mu
 m._run(1, 30)
 m.chain_.synchronize()
 L = _lib.load()
-w = np.zeros((6, 512, 2), dtype=np.uint64)
-L.dlsm_debug_hdp_tail_timing.restype = C.c_int
-L.dlsm_debug_hdp_tail_timing.argtypes = [C.c_void_p]
-assert L.dlsm_debug_hdp_tail_timing(w.ctypes.data) == 0
+w = read_stamps(L, 'hdp_t', (6, 512, 2))
 w = w.astype(np.int64)
 names = ['stage1', 'stage2', 'stage3', 'hypers', 'logp_sums', 'finalize']
 n_tab = (T * K * K + 7) // 8 if False else None
@@ -53,16 +50,10 @@ for i, nm in enumerate(names):
                'slowest_workgroups[(blockIdx, entry, exit)]': [(int(idx[j]), round(float(ent[j]), 2), round(float(ext[j]), 2)) for j in order]}
     print(nm, json.dumps(out[nm]))
 # phases of the globals' workgroup of stage 2, relative to its entry
-ph = np.zeros((16, 2), dtype=np.uint64)
-try:
-    L.dlsm_debug_hdp_globals_phases.restype = C.c_int
-    L.dlsm_debug_hdp_globals_phases.argtypes = [C.c_void_p]
-    if L.dlsm_debug_hdp_globals_phases(ph.ctypes.data) == 0:
-        p0 = ph[[0, 2, 3, 4], 0].astype(np.int64)
-        key = 'stage2_globals_phases_us[entry, binomials + column sums + pre-drawn variates done, beta drawn, exit]'
-        out[key] = [round(float(v - p0[0]) * 0.01, 2) for v in p0]
-        print('globals phases', out[key])
-except AttributeError:
-    pass
+ph = read_stamps(L, 'hdp_phase', (16, 2))
+p0 = ph[[0, 2, 3, 4], 0].astype(np.int64)
+key = 'stage2_globals_phases_us[entry, binomials + column sums + pre-drawn variates done, beta drawn, exit]'
+out[key] = [round(float(v - p0[0]) * 0.01, 2) for v in p0]
+print('globals phases', out[key])
 if len(sys.argv) > 2:
     json.dump(out, open(sys.argv[2], 'w'), indent=1)

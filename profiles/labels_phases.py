@@ -3,7 +3,6 @@ wavefront (= node) entry, transition matrices staged in LDS, the T x K table bui
 messages done, forward sampling done.
     python profiles/labels_phases.py tmp_timing/libtiming.so [out.json]
 """
-import ctypes as C
 import json
 import os
 import sys
@@ -17,6 +16,7 @@ from dynetlsm_amd import _lib  # noqa: E402
 _lib.LIB_PATH = os.path.abspath(sys.argv[1])
 from dynetlsm_amd import DynamicNetworkHDPLPCM  # noqa: E402
 from dynetlsm_amd.synthetic import synthetic_hdp_network  # noqa: E402
+from stamps import read_stamps  # noqa: E402  (profiles/stamps.py)
 
 T, N, D, K = 10, 2000, 2, 20
 net = synthetic_hdp_network(T=T, N=N, D=D, density=0.03, seed=0)
@@ -30,10 +30,7 @@ m._prepare(net['Y'], init=dict(X=net['X_init'], intercept=[net['intercept']], mu
 m._run(1, 30)
 m.chain_.synchronize()
 L = _lib.load()
-w = np.zeros((4096, 6), dtype=np.uint64)
-L.dlsm_debug_labels_timing.restype = C.c_int
-L.dlsm_debug_labels_timing.argtypes = [C.c_void_p]
-assert L.dlsm_debug_labels_timing(w.ctypes.data) == 0
+w = read_stamps(L, 'lab_t', (4096, 6))
 w = w[:, :5].astype(np.int64)
 w = w[w[:, 0] != 0]          # one row per wavefront (per node) or per workgroup (16 nodes)
 t0 = w[:, 0].min()

@@ -3,7 +3,6 @@
 SIMDs and how long the busiest one works.
     python profiles/loglik_timing.py tmp_timing/libtiming.so [out.json]
 """
-import ctypes as C
 import json
 import os
 import sys
@@ -17,6 +16,7 @@ from dynetlsm_amd import _lib  # noqa: E402
 _lib.LIB_PATH = os.path.abspath(sys.argv[1])
 from dynetlsm_amd import Chain, SamplerGrid  # noqa: E402
 from dynetlsm_amd.synthetic import synthetic_lsm_network  # noqa: E402
+from stamps import read_stamps  # noqa: E402  (profiles/stamps.py)
 
 T, N, D = 10, 2000, 2
 net = synthetic_lsm_network(T, N, D, density=0.03, seed=0)
@@ -32,10 +32,7 @@ ch.trace_alloc(64, logp0=0.0)
 ch.lsm_run(1, 40, procrustes_ref=0)
 ch.synchronize()
 L = _lib.load()
-w = np.zeros((8192, 3), dtype=np.uint64)
-L.dlsm_debug_loglik_timing.restype = C.c_int
-L.dlsm_debug_loglik_timing.argtypes = [C.c_void_p]
-assert L.dlsm_debug_loglik_timing(w.ctypes.data) == 0
+w = read_stamps(L, 'll_t', (8192, 3))
 w = w[w[:, 0] > 0].astype(np.int64)
 t0 = w[:, 0].min()
 ent = (w[:, 0] - t0) * 0.01

@@ -15,7 +15,6 @@ first trip of 64 neighbours done, last trip done, record stored (= exit: the H f
 record stored, kernel start, exit.)  Resolver stamps: 0 entry, 1 H block + records in LDS, 2 cross products
 applied, 3 fixed point reached, 4 exit.
 """
-import ctypes as C
 import json
 import os
 import sys
@@ -29,6 +28,7 @@ from dynetlsm_amd import _lib  # noqa: E402
 _lib.LIB_PATH = os.path.abspath(sys.argv[1])
 from dynetlsm_amd import Chain, SamplerGrid  # noqa: E402
 from dynetlsm_amd.synthetic import synthetic_lsm_network  # noqa: E402
+from stamps import read_stamps  # noqa: E402  (profiles/stamps.py)
 
 T, N, D = 10, 2000, 2
 net = synthetic_lsm_network(T, N, D, density=0.03, seed=0)
@@ -45,12 +45,8 @@ ch.lsm_run(1, 40, procrustes_ref=0)
 ch.synchronize()
 
 L = _lib.load()
-items = np.zeros((24, 4096, 6), dtype=np.uint64)
-res = np.zeros((24, 32, 5), dtype=np.uint64)
-L.dlsm_debug_pipe_timing.restype = C.c_int
-L.dlsm_debug_pipe_timing.argtypes = [C.c_void_p, C.c_void_p]
-rc = L.dlsm_debug_pipe_timing(items.ctypes.data, res.ctypes.data)
-assert rc == 0, rc
+items = read_stamps(L, 'pipe_item_t', (24, 4096, 6))
+res = read_stamps(L, 'pipe_res_t', (24, 32, 5))
 
 out = []
 for l in range(24):

@@ -180,3 +180,18 @@ def test_n_features_beyond_the_kernels_is_a_value_error_before_any_device_call()
             est.fit(Y)
     with pytest.raises(ValueError, match='n_features=9'):
         da.Chain(2, 6, 9, 'undirected')
+
+
+def test_phase_stamps_are_known_to_one_header_and_one_export():
+    """the in-kernel phase stamps (-DDLSM_PIPE_TIMING) are woven in through kernel_stamps.hpp alone: no other
+    source tests the switch, capi.hip once (its reader), and the reader is no part of the product's C-ABI"""
+    csrc = os.path.join(ROOT, 'dynetlsm_amd', 'csrc')
+    sites = {}
+    for name in sorted(os.listdir(csrc)):
+        lines = open(os.path.join(csrc, name), errors='replace').read().splitlines()
+        sites[name] = [l for l in lines if re.match(r'\s*#', l) and 'DLSM_PIPE_TIMING' in l]
+    assert 'kernel_stamps.hpp' in sites and len(sites) > 20
+    assert sites.pop('kernel_stamps.hpp')
+    assert len(sites.pop('capi.hip')) == 1
+    assert {k: v for k, v in sites.items() if v} == {}
+    assert 'dlsm_debug_' not in open(os.path.join(ROOT, 'include', 'dynetlsm_hip.h')).read()
