@@ -16,10 +16,11 @@ c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
 c_i32_p = C.POINTER(C.c_int32)
 c_u32_p = C.POINTER(C.c_uint32)
+c_u64_p = C.POINTER(C.c_uint64)
 handle_t = C.c_void_p
 
 (K_LOGLIK, K_SWEEP, K_CENTER, K_LABELS, K_FINALIZE, K_SWEEP_EVAL, K_SWEEP_RESOLVE,
- K_INIT, K_HDP_TAIL) = range(9)
+ K_INIT, K_HDP_TAIL, K_SCORE_ACCUMULATE, K_SCORE_CLEAR, K_SCORE_SCAN) = range(12)
 UNDIRECTED, DIRECTED, DIRECTED_CASE_CONTROL = 0, 1, 2
 
 
@@ -161,6 +162,8 @@ SIGNATURES = {
     'dlsm_gof_observed': (C.c_int, [handle_t, c_u32_p, c_i64_p]),
     'dlsm_ic_accumulate': (C.c_int, [handle_t, c_u32_p, c_double_p, c_double_p, c_double_p, C.c_int,
                                      c_double_p, c_double_p, c_double_p]),
+    'dlsm_score_accumulate': (C.c_int, [handle_t, c_u32_p, c_u32_p, c_double_p, c_double_p, c_double_p, C.c_int,
+                                        c_u64_p, c_double_p]),
     'dlsm_set_missing': (C.c_int, [handle_t, c_i32_p, C.c_int64]),
     'dlsm_impute_missing': (C.c_int, [handle_t, C.c_uint32, C.c_int]),
     'dlsm_missing_sampling': (C.c_int, [handle_t, C.c_int, C.c_int]),

@@ -31,6 +31,7 @@
 #include "kernels_forecast.hpp"
 #include "kernels_gof.hpp"
 #include "kernels_ic.hpp"
+#include "kernels_score.hpp"
 #include "kernels_missing.hpp"
 #include "host_draws.hpp"
 
@@ -2205,6 +2206,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_forecast.hpp"
 #include "capi_gof.hpp"
 #include "capi_ic.hpp"
+#include "capi_score.hpp"
 #include "capi_hdp.hpp"
 
 extern "C" int dlsm_host_sample_tables(void *numpy_bitgen, int T, int K, const double *n,

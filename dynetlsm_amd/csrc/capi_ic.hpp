@@ -17,6 +17,27 @@ std::vector<int2> ic_tiles(int N, int TI, bool directed) {
     return tiles;
 }
 
+// what the passes over posterior samples ask of their inputs: the padding bits and the diagonal of the packed
+// network are zero, the radii (directed; S * N) positive
+int ic_check_inputs(dlsm_chain *h, const uint32_t *bits, const double *radii, int S) {
+    const int T = h->T, N = h->N, W = h->W;
+    for (size_t row = 0; row < (size_t)T * N; ++row) {
+        const uint32_t *r = bits + row * W;
+        const int i = (int)(row % N);
+        if ((r[i >> 5] >> (i & 31)) & 1u)
+            FAIL(h, DLSM_E_DATA, "network has a self-loop (t=%d, i=%d)", (int)(row / N), i);
+        for (int w = N >> 5; w < W; ++w) {
+            const int lo = 32 * w;
+            const uint32_t pad = lo >= N ? 0xFFFFFFFFu : ~((1u << (N - lo)) - 1u);
+            if (r[w] & pad) FAIL(h, DLSM_E_DATA, "padding bits beyond column N-1 must be zero");
+        }
+    }
+    if (h->model != DLSM_UNDIRECTED)
+        for (size_t k = 0; k < (size_t)S * N; ++k)
+            if (!(radii[k] > 0.0)) FAIL(h, DLSM_E_DATA, "radii must be positive (sample %zu, node %zu)", k / N, k % N);
+    return DLSM_OK;
+}
+
 template <int D>
 void ic_launch(dlsm_chain *h, bool directed, dim3 grid, const double *Xs, const double *ic, const double *radii,
                const uint32_t *bits, const int2 *tiles, int n_tiles, int L, int S, double *part_tot,
@@ -41,21 +62,7 @@ int dlsm_ic_accumulate(dlsm_chain *h, const uint32_t *bits, const double *Xs, co
     NEED(h, S >= 1, "needs at least one sample");
     const int T = h->T, N = h->N, D = h->D, W = h->W;
     const size_t net_words = (size_t)N * W;
-    // the padding bits and the diagonal are zero
-    for (size_t row = 0; row < (size_t)T * N; ++row) {
-        const uint32_t *r = bits + row * W;
-        const int i = (int)(row % N);
-        if ((r[i >> 5] >> (i & 31)) & 1u)
-            FAIL(h, DLSM_E_DATA, "network has a self-loop (t=%d, i=%d)", (int)(row / N), i);
-        for (int w = N >> 5; w < W; ++w) {
-            const int lo = 32 * w;
-            const uint32_t pad = lo >= N ? 0xFFFFFFFFu : ~((1u << (N - lo)) - 1u);
-            if (r[w] & pad) FAIL(h, DLSM_E_DATA, "padding bits beyond column N-1 must be zero");
-        }
-    }
-    if (directed)
-        for (size_t k = 0; k < (size_t)S * N; ++k)
-            if (!(radii[k] > 0.0)) FAIL(h, DLSM_E_DATA, "radii must be positive (sample %zu, node %zu)", k / N, k % N);
+    if (int rc = ic_check_inputs(h, bits, radii, S)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const int TI = D <= 4 ? IcPlan<1>::TI : IcPlan<8>::TI;
     const std::vector<int2> tiles = ic_tiles(N, TI, directed);

@@ -820,6 +820,45 @@ class Chain(object):
             int(S), _p(totals), _p(sample_loglik), _p(pw) if want_pointwise else None))
         return (totals, sample_loglik, pw) if want_pointwise else (totals, sample_loglik)
 
+    # -- in-sample scores (no reference counterpart) --------------------------------------------
+    def score_accumulate(self, bits, Xs, intercepts, radii=None, mask=None):
+        """Rank statistics and log-loss of the posterior-mean edge probability of the packed network
+        ``bits`` over the S samples (arguments as ``ic_accumulate``), computed on the device without
+        sorting (csrc/kernels_score.hpp).  ``mask``: packed like ``bits``, a set bit excludes the dyad
+        (undirected chains: either of (i, j), (j, i)).  Returns ``counts`` (T + 1, 4) uint64 - per time
+        step and, in row T, pooled: n_pos, n_neg, u2, ties - and ``logloss_sum`` (T,);
+        ``scores.scores_from_counts`` turns them into AUC, its bound and the mean log-loss."""
+        shape = (self.T, self.N, packed_row_words(self.N))
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        if bits.shape != shape:
+            raise ValueError('bits has shape %s, expected %s' % (bits.shape, shape))
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint32)
+            if mask.shape != shape:
+                raise ValueError('mask has shape %s, expected %s' % (mask.shape, shape))
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        S = Xs.shape[0]
+        if S < 1:
+            raise ValueError('needs at least one sample')
+        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
+        b = np.asarray(intercepts, dtype=np.float64)
+        if b.ndim == 1 and self.model == UNDIRECTED:
+            b = np.stack([b, np.zeros_like(b)], axis=1)
+        b = _f64(b, (S, 2), 'intercepts')
+        if self.model == UNDIRECTED:
+            r = None
+        else:
+            if radii is None:
+                raise ValueError('directed models need radii')
+            r = _f64(radii, (S, self.N), 'radii')
+        counts = np.zeros((self.T + 1, 4), dtype=np.uint64)
+        logloss_sum = np.zeros(self.T)
+        self._ck(self._L.dlsm_score_accumulate(
+            self._h, bits.ctypes.data_as(_lib.c_u32_p),
+            mask.ctypes.data_as(_lib.c_u32_p) if mask is not None else None, _p(Xs), _p(b),
+            _p(r) if r is not None else None, int(S), counts.ctypes.data_as(_lib.c_u64_p), _p(logloss_sum)))
+        return counts, logloss_sum
+
     def profile_enable(self, on=True):
         self._ck(self._L.dlsm_profile_enable(self._h, int(on)))
 

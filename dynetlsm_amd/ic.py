@@ -128,20 +128,9 @@ def _two_intercepts(ic):
     return np.ascontiguousarray(ic[:, :2])
 
 
-def information_criteria(model, n_samples=None, pointwise=False):
-    """WAIC and DIC of a fitted ``DynamicNetworkLSM`` (undirected, directed or case-control),
-    ``DynamicNetworkHDPLPCM`` or ``DynamicNetworkLPCM``, for comparing fits of the same network
-    (``n_features``, directed against undirected, LSM against the clustered models).
-
-    The samples are all kept rows of the trace (after the burn-in), or ``n_samples`` of them evenly
-    spaced as ``posterior_predictive_check`` picks them.  The likelihood is the exact one of the
-    model, also for case-control fits.  The observed network is ``Y_fit_``, the network the chain was
-    fit to, over all its dyads: if the data had missing dyads, these are their imputed values.
-    ``pointwise=True`` also returns the per-dyad ``lppd`` and ``p_waic`` (two (T, N, N) arrays), which
-    ``compare_information_criteria`` needs.
-
-    Returns an ``ICResult``.
-    """
+def _sample_rows(model, n_samples):
+    """the trace rows a pass over the posterior uses: all kept rows (after the burn-in), or
+    ``n_samples`` of them evenly spaced as ``posterior_predictive_check`` picks them"""
     if not hasattr(model, 'Y_fit_') or not hasattr(model, 'intercepts_'):
         raise ValueError('Model not fit.')
     n_rows = np.shape(model.intercepts_)[0]
@@ -156,6 +145,24 @@ def information_criteria(model, n_samples=None, pointwise=False):
             raise ValueError('n_samples=%d exceeds the %d kept samples of the trace'
                              % (n_samples_i, n_rows - start))
         ids = np.round(np.linspace(start, n_rows - 1, n_samples_i)).astype(np.int64)
+    return ids
+
+
+def information_criteria(model, n_samples=None, pointwise=False):
+    """WAIC and DIC of a fitted ``DynamicNetworkLSM`` (undirected, directed or case-control),
+    ``DynamicNetworkHDPLPCM`` or ``DynamicNetworkLPCM``, for comparing fits of the same network
+    (``n_features``, directed against undirected, LSM against the clustered models).
+
+    The samples are all kept rows of the trace (after the burn-in), or ``n_samples`` of them evenly
+    spaced as ``posterior_predictive_check`` picks them.  The likelihood is the exact one of the
+    model, also for case-control fits.  The observed network is ``Y_fit_``, the network the chain was
+    fit to, over all its dyads: if the data had missing dyads, these are their imputed values.
+    ``pointwise=True`` also returns the per-dyad ``lppd`` and ``p_waic`` (two (T, N, N) arrays), which
+    ``compare_information_criteria`` needs.
+
+    Returns an ``ICResult``.
+    """
+    ids = _sample_rows(model, n_samples)
     directed = bool(model.is_directed)
     Xs = np.ascontiguousarray(model.Xs_[ids], dtype=np.float64)
     S, T, N, D = Xs.shape

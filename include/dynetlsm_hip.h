@@ -420,6 +420,27 @@ int dlsm_ic_accumulate(dlsm_chain *h, const uint32_t *bits, const double *Xs, co
                        const double *radii, int S, double *totals, double *sample_loglik,
                        double *pointwise);
 
+/* ---- in-sample scores (AUC, log-loss of the posterior mean) ------------- */
+/* No reference counterpart (metrics.py:10-24 sorts the probabilities of one sample on the host).  For every
+ * dyad of the packed network `bits` (as dlsm_ic_accumulate takes it: the same dyads, the same linear predictor
+ * eta, the same samples Xs S*T*N*D, intercepts S*2, radii S*N or NULL) whose bit in `mask` (NULL, or T*N*W
+ * uint32 packed like the network; undirected handles: either of (i, j), (j, i)) is not set, the posterior-mean
+ * probability pbar = mean_s expit(eta_s) in float64 and its rank key
+ *   key = max(bits((float)pbar) >> 8, 0x200000)        (2^15 bins per octave; pbar <= 2^-63 share one bin)
+ * are formed in one pass, and the keys are counted per class into histograms of 0x3F8000 - 0x200000 + 1 bins
+ * in device memory (time steps in groups, within a fixed budget).  Nothing of size T*N*N is stored or sorted.
+ *   counts      (T+1)*4 uint64: per time step, row T pooled over time, n_pos, n_neg (scored dyads with
+ *               y = 1 / 0), u2 = sum_b pos_b (2 cumneg_b + neg_b) (twice the Mann-Whitney statistic of the
+ *               keys, ties counted half: auc = u2 / (2 n_pos n_neg)) and ties = sum_b pos_b neg_b (the AUC of
+ *               the keys is within ties / (2 n_pos n_neg) of the exact AUC of pbar)
+ *   logloss_sum T: sum over the scored dyads of -[y log pbar + (1 - y) log(1 - pbar)], finite for any finite eta
+ * The counts are exact integers (the same on every call, whatever the order of the atomics); the log-loss sums
+ * are taken in a fixed order.  T*N*(N-1) (undirected: half) >= 2^32 dyads, or samples that do not fit the
+ * device -> DLSM_E_LIMIT; a set diagonal or padding bit of `bits`, a radius <= 0 -> DLSM_E_DATA. */
+int dlsm_score_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *mask, const double *Xs,
+                          const double *intercepts, const double *radii, int S, uint64_t *counts,
+                          double *logloss_sum);
+
 /* ---- missing dyads: the data-augmentation step --------------------------- */
 /* lsm.py:525-545 / hdp_lpcm.py:1025-1049 draw y_ij ~ Bernoulli(p_ij) for the -1 coded dyads every
  * iteration (their write-back into the network is lost in a fancy-index copy; hdp_lpcm.py:1155-1156
@@ -469,7 +490,10 @@ enum {
     DLSM_K_SWEEP_RESOLVE = 6,  /* k_spec_resolve launches */
     DLSM_K_INIT = 7,           /* every kernel of the dlsm_init_* calls */
     DLSM_K_HDP_TAIL = 8,       /* dlsm_hdp_run: everything after the label update */
-    DLSM_K_COUNT = 9
+    DLSM_K_SCORE_ACCUMULATE = 9,   /* dlsm_score_accumulate: k_score_accumulate (sample loop + histogram) */
+    DLSM_K_SCORE_CLEAR = 10,       /* ... the histograms' hipMemsetAsync */
+    DLSM_K_SCORE_SCAN = 11,        /* ... k_score_scan (pooling included) and the log-loss reduction */
+    DLSM_K_COUNT = 12
 };
 /* when enabled every launch of the kernel classes above is bracketed by HIP
  * events on the handle's stream; read returns accumulated ms and launches */
