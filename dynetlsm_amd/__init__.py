@@ -16,10 +16,12 @@ from . import model_selection  # noqa
 from .gof import posterior_predictive_check, GofResult  # noqa
 from .ic import information_criteria, compare_information_criteria, ICResult  # noqa
 from .scores import in_sample_scores, ScoreResult  # noqa
+from . import forecast  # noqa  (the one-step module; calling it is forecast_paths.forecast)
+from .forecast_paths import ForecastResult  # noqa
 
 __version__ = '0.1.0'
 __all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
            'DynamicNetworkLSM', 'DynamicNetworkHDPLPCM', 'DynamicNetworkLPCM',
            'DirectedCaseControlSampler', 'posterior_predictive_check', 'GofResult',
            'information_criteria', 'compare_information_criteria', 'ICResult',
-           'in_sample_scores', 'ScoreResult']
+           'in_sample_scores', 'ScoreResult', 'forecast', 'ForecastResult']

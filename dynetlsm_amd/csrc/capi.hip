@@ -29,6 +29,7 @@
 #include "kernels_init.hpp"
 #include "kernels_post.hpp"
 #include "kernels_forecast.hpp"
+#include "kernels_forecast_paths.hpp"
 #include "kernels_gof.hpp"
 #include "kernels_ic.hpp"
 #include "kernels_score.hpp"
@@ -2207,6 +2208,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_gof.hpp"
 #include "capi_ic.hpp"
 #include "capi_score.hpp"
+#include "capi_forecast_paths.hpp"
 #include "capi_hdp.hpp"
 
 extern "C" int dlsm_host_sample_tables(void *numpy_bitgen, int T, int K, const double *n,

@@ -859,6 +859,64 @@ class Chain(object):
             _p(r) if r is not None else None, int(S), counts.ctypes.data_as(_lib.c_u64_p), _p(logloss_sum)))
         return counts, logloss_sum
 
+    # -- multi-step posterior predictive forecasts (the reference: one step, undirected, on the host) ----
+    def forecast_paths(self, X0, intercepts, radii=None, z0=None, trans=None, mu=None, sigma=None, lmbda=None,
+                       sigma_sq=0.0, horizon=1, seed=0, first_index=0, batch=0, want_paths=False,
+                       want_labels=False):
+        """One trajectory of ``horizon`` future time steps per posterior sample, drawn and averaged on the
+        device (csrc/kernels_forecast_paths.hpp).  ``X0`` (S, N, D): the samples' last time step;
+        ``intercepts`` (S,) or (S, 2); ``radii`` (S, N) (directed and case-control chains).  With ``z0``
+        (S, N) the mixture dynamics: ``trans`` (S, K, K) raw transition rows, ``mu`` (S, K, D), ``sigma``
+        (S, K) variances, ``lmbda`` (S,); without it the random walk of variance ``sigma_sq``.  Sample s
+        uses RNG index ``first_index + s``: results do not depend on how the samples are split across calls
+        or on ``batch`` (samples per device batch, 0: automatic).  Returns ``(probas, paths, labels)``:
+        (H, N, N) mean edge probabilities over the S samples, (S, H, N, D) positions if ``want_paths`` and
+        (S, H, N) int32 labels if ``want_labels`` (mixture only), else None."""
+        X0 = np.ascontiguousarray(X0, dtype=np.float64)
+        S = X0.shape[0]
+        if S < 1:
+            raise ValueError('needs at least one sample')
+        X0 = _f64(X0, (S, self.N, self.D), 'X0')
+        H = int(horizon)
+        if H != horizon or H < 1:
+            raise ValueError('horizon must be a positive integer, got %r' % (horizon,))
+        b = np.asarray(intercepts, dtype=np.float64)
+        if b.ndim == 1 and self.model == UNDIRECTED:
+            b = np.stack([b, np.zeros_like(b)], axis=1)
+        b = _f64(b, (S, 2), 'intercepts')
+        if self.model == UNDIRECTED:
+            r = None
+        else:
+            if radii is None:
+                raise ValueError('directed models need radii')
+            r = _f64(radii, (S, self.N), 'radii')
+        if z0 is None:
+            if want_labels:
+                raise ValueError('the random walk has no labels')
+            K, z, w, m, sg, lm = 0, None, None, None, None, None
+        else:
+            if trans is None or mu is None or sigma is None or lmbda is None:
+                raise ValueError('the mixture needs trans, mu, sigma and lmbda')
+            w = np.ascontiguousarray(trans, dtype=np.float64)
+            K = int(w.shape[-1])
+            z = _i32(z0, (S, self.N), 'z0')
+            w = _f64(w, (S, K, K), 'trans')
+            m = _f64(mu, (S, K, self.D), 'mu')
+            sg = _f64(sigma, (S, K), 'sigma')
+            lm = _f64(np.ravel(lmbda), (S,), 'lmbda')
+        probas = np.zeros((H, self.N, self.N))
+        paths = np.zeros((S, H, self.N, self.D)) if want_paths else None
+        labels = np.zeros((S, H, self.N), dtype=np.int32) if want_labels else None
+
+        def ptr(a):
+            return _p(a) if a is not None else None
+
+        self._ck(self._L.dlsm_forecast_paths(
+            self._h, _p(X0), _p(b), ptr(r), ptr(z), ptr(w), ptr(m), ptr(sg), ptr(lm), K, float(sigma_sq), H, int(S),
+            C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(first_index)), int(batch), _p(probas),
+            ptr(paths), ptr(labels)))
+        return probas, paths, labels
+
     def profile_enable(self, on=True):
         self._ck(self._L.dlsm_profile_enable(self._h, int(on)))
 

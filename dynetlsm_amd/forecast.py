@@ -5,6 +5,9 @@ The O(n_samples N^2) accumulations run on the device (``Chain.forecast_mean_prob
 ``Chain.forecast_marginal``); label / position draws stay on the host in the reference's
 MT19937 order, as do the O(n_samples N K) plug-in positions and mixture densities.
 """
+import sys
+import types
+
 import numpy as np
 
 from .posterior import renormalize_weights
@@ -192,3 +195,17 @@ def lpcm_forecast_probas(model, chain, n_samples=5000, rng=None, batch=512):
                        for _ in range(ns)])
         probas += chain.forecast_mean_probas(Xs, b, zero_diag=True) * (ns / float(n_samples))
     return probas
+
+
+# ---------------------------------------------------------------------------
+# ``dynetlsm_amd.forecast`` is this module AND the package's forecast function: calling the module runs the
+# multi-step posterior predictive forecast of forecast_paths.py (``da.forecast(model, horizon=3)``), while
+# ``from dynetlsm_amd import forecast as fc; fc.forecast_probas_map(...)`` keeps reaching the one-step functions.
+# ---------------------------------------------------------------------------
+class _ForecastModule(types.ModuleType):
+    def __call__(self, model, horizon=1, **kw):
+        from .forecast_paths import forecast
+        return forecast(model, horizon=horizon, **kw)
+
+
+sys.modules[__name__].__class__ = _ForecastModule

@@ -150,6 +150,12 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
     def forecast_probas_pp_(self):
         return fc.forecast_probas_pp(self, self._forecast_ready())
 
+    def forecast(self, horizon=1, **kw):
+        """posterior predictive forecast of the next ``horizon`` networks, drawn on the device; undirected and
+        directed fits (``forecast_paths.forecast``)"""
+        from .forecast_paths import forecast
+        return forecast(self, horizon=horizon, **kw)
+
     # ------------------------------------------------------------------ init
     def _init_sampler(self, Y, rng, init):
         """hdp_lpcm.py:48-141 : LSM warm start, longitudinal k-means, weights"""

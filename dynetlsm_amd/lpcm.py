@@ -99,6 +99,12 @@ class DynamicNetworkLPCM(FittedQuantities):
     def forecast_probas(self, n_samples=5000):
         return fc.lpcm_forecast_probas(self, self._forecast_ready(), n_samples=n_samples)
 
+    def forecast(self, horizon=1, **kw):
+        """posterior predictive forecast of the next ``horizon`` networks, drawn on the device; undirected and
+        directed fits (``forecast_paths.forecast``)"""
+        from .forecast_paths import forecast
+        return forecast(self, horizon=horizon, **kw)
+
     # ------------------------------------------------------------------ init
     def _init_sampler(self, Y, Y_raw, rng, init):
         """lpcm.py:45-132: LSM warm start, longitudinal k-means, empirical initial

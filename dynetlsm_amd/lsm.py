@@ -138,6 +138,12 @@ class DynamicNetworkLSM(FittedQuantities):
     def n_burn_(self):
         return (self.burn or 0) + (self.tune or 0)
 
+    def forecast(self, horizon=1, **kw):
+        """posterior predictive forecast of the next ``horizon`` networks, drawn on the device: the random
+        walk of variance ``sigma_sq`` from every kept sample's last time step (``forecast_paths.forecast``)"""
+        from .forecast_paths import forecast
+        return forecast(self, horizon=horizon, **kw)
+
     # -- fit ------------------------------------------------------------------
     def fit(self, Y, init=None):
         """Sample the posterior given the dynamic network ``Y`` (T, N, N),

@@ -441,6 +441,30 @@ int dlsm_score_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *m
                           const double *intercepts, const double *radii, int S, uint64_t *counts,
                           double *logloss_sum);
 
+/* ---- multi-step posterior predictive forecasts --------------------------- */
+/* The reference has only the one-step undirected form (hdp_lpcm.py:555-626, drawn on the host).  One
+ * trajectory of H future time steps per sample s, started at the sample's last time step X0 S*N*D:
+ *   random walk (z0 == NULL, K = 0):  x_h = x_{h-1} + sqrt(sigma_sq) eps
+ *   mixture (z0 S*N int32 labels of the last step, trans S*K*K raw transition rows - the device divides by
+ *   the row sum -, mu S*K*D, sigma S*K variances, lmbda S):
+ *       z_h ~ Categorical(trans[s][z_{h-1}][:]),  x_h = lmbda mu[z_h] + (1 - lmbda) x_{h-1} + sqrt(sigma[z_h]) eps
+ * and probas H*N*N: probas[h][i][j] = (1/S) sum_s expit(eta_s(h, i, j)), eta = b - |x_i - x_j| for undirected
+ * handles (intercepts S*2, [s][0] read) and the directed model of metrics.py:57-60 with the sample's
+ * intercepts and radii S*N, held fixed over the horizon, for directed and case-control handles; diagonal 0.
+ * Sample s uses RNG index first_index + s: Philox4x32-10 keyed by `seed` at counter (node, h | draw << 16,
+ * index, 9), h = 1..H; draw 0 gives the label uniform (the label is the smallest k with u * c_{K-1} <= c_k,
+ * c the running sum of the row), draw 1 + d/2 the Box-Muller pair of coordinates d, d + 1.  Results do not
+ * depend on how the samples are split across calls or batches (batch = samples per device batch, 0:
+ * automatic, bounded scratch; probas is the mean over the S samples of the call).
+ *   paths   NULL or S*H*N*D: the drawn positions
+ *   labels  NULL or S*H*N int32: the drawn labels (mixture only)
+ * H outside 1..65535, K < 1 for the mixture, first_index + S > 2^32 -> DLSM_E_ARG; a label outside [0, K), a
+ * radius <= 0, a sigma < 0, a negative weight or a row sum that is not positive -> DLSM_E_DATA. */
+int dlsm_forecast_paths(dlsm_chain *h, const double *X0, const double *intercepts, const double *radii,
+                        const int32_t *z0, const double *trans, const double *mu, const double *sigma,
+                        const double *lmbda, int K, double sigma_sq, int H, int S, uint64_t seed,
+                        uint32_t first_index, int batch, double *probas, double *paths, int32_t *labels);
+
 /* ---- missing dyads: the data-augmentation step --------------------------- */
 /* lsm.py:525-545 / hdp_lpcm.py:1025-1049 draw y_ij ~ Bernoulli(p_ij) for the -1 coded dyads every
  * iteration (their write-back into the network is lost in a fancy-index copy; hdp_lpcm.py:1155-1156
