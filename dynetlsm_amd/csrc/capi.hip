@@ -31,6 +31,7 @@
 #include "kernels_forecast.hpp"
 #include "kernels_forecast_paths.hpp"
 #include "kernels_gof.hpp"
+#include "kernels_gof_dynamic.hpp"
 #include "kernels_ic.hpp"
 #include "kernels_score.hpp"
 #include "kernels_missing.hpp"
@@ -2206,6 +2207,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_post.hpp"
 #include "capi_forecast.hpp"
 #include "capi_gof.hpp"
+#include "capi_gof_dynamic.hpp"
 #include "capi_ic.hpp"
 #include "capi_score.hpp"
 #include "capi_forecast_paths.hpp"

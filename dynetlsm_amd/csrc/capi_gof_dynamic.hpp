@@ -1,0 +1,196 @@
+// C-ABI of the goodness-of-fit statistics over time (kernels_gof_dynamic.hpp; included by capi.hip after
+// capi_gof.hpp, whose draws, batching and lane choice it shares).  The reference has no counterpart.
+#pragma once
+
+namespace {
+
+// int64 entries per sample of the three records
+struct GofDynSizes {
+    size_t overlap, steps, geodesic;
+    GofDynSizes(int T, int N, bool temporal, bool geo)
+        : overlap(temporal ? (size_t)T * T : 0), steps(temporal ? (size_t)(T - 1) * 2 * N : 0),
+          geodesic(geo ? (size_t)T * N : 0) {}
+    size_t total() const { return overlap + steps + geodesic; }
+};
+
+int gof_dynamic_check(dlsm_chain *h, bool geo) {
+    NEED(h, h->T <= 65535, "T=%d: the statistics over time hold at most 65535 time steps", h->T);
+    if (geo && h->W > 64 * GOF_GEO_MAX_WORDS)
+        FAIL(h, DLSM_E_LIMIT, "N=%d: the geodesic distances hold at most %d nodes", h->N, 2048 * GOF_GEO_MAX_WORDS);
+    return DLSM_OK;
+}
+
+template <int NW>
+void gof_geodesic_launch_nw(dlsm_chain *h, const uint32_t *rows, int nets, int directed, int64_t *dgeo) {
+    const int N = h->N;
+    const int nbx = std::max(1, std::min((N + 3) / 4, 8192 / nets));
+    hipLaunchKernelGGL((k_gof_geodesic<NW>), dim3(nbx, nets), dim3(256), 0, h->stream, rows, N, h->W, directed,
+                       dgeo);
+}
+
+// the records of n samples' networks: rows (and trows, directed) [n * T][N][W] on the device -> drec, the
+// n samples' overlap [n][T][T], then steps [n][T-1][2N], then geodesic [n * T][N]; zeroed here
+int gof_dynamic_launch(dlsm_chain *h, const uint32_t *rows, const uint32_t *trows, int n, bool temporal,
+                       bool geo, int64_t *drec) {
+    const int T = h->T, N = h->N, W = h->W;
+    const GofDynSizes sz(T, N, temporal, geo);
+    const int directed = h->model != DLSM_UNDIRECTED;           // trows: read by the steps alone
+    HIPCHK(h, hipMemsetAsync(drec, 0, (size_t)n * sz.total() * sizeof(int64_t), h->stream));
+    if (temporal) {
+        // four quad-words per thread
+        const unsigned gx = (unsigned)(((size_t)N * W / 4 + 1023) / 1024);
+        hipLaunchKernelGGL(k_gof_overlap, dim3(gx, T, n), dim3(256), 0, h->stream, rows, T, N, W, directed, drec);
+        HIPCHK(h, hipGetLastError());
+        if (T > 1) {
+            const int nets = n * (T - 1);
+            const int nbx = std::max(1, std::min(N, 8192 / nets));
+            hipLaunchKernelGGL(k_gof_step, dim3(nbx, nets), dim3(256), 0, h->stream, rows, trows, T, N, W,
+                               gof_lanes_per_row(W), drec + (size_t)n * sz.overlap);
+            HIPCHK(h, hipGetLastError());
+        }
+    }
+    if (geo) {
+        int64_t *dgeo = drec + (size_t)n * (sz.overlap + sz.steps);
+        const int nw = (W + 63) / 64;
+        if (nw <= 1) gof_geodesic_launch_nw<1>(h, rows, n * T, directed, dgeo);
+        else if (nw <= 2) gof_geodesic_launch_nw<2>(h, rows, n * T, directed, dgeo);
+        else if (nw <= 4) gof_geodesic_launch_nw<4>(h, rows, n * T, directed, dgeo);
+        else if (nw <= 8) gof_geodesic_launch_nw<8>(h, rows, n * T, directed, dgeo);
+        else gof_geodesic_launch_nw<GOF_GEO_MAX_WORDS>(h, rows, n * T, directed, dgeo);
+        HIPCHK(h, hipGetLastError());
+    }
+    return DLSM_OK;
+}
+
+// device records of n samples -> the caller's arrays (at sample s0); the stream is synchronised here and the
+// lower triangle of every overlap is filled from the upper one
+int gof_dynamic_fetch(dlsm_chain *h, const int64_t *drec, int n, size_t s0, bool temporal, bool geo,
+                      int64_t *overlap, int64_t *steps, int64_t *geodesic) {
+    const int T = h->T;
+    const GofDynSizes sz(T, h->N, temporal, geo);
+    if (temporal) {
+        HIPCHK(h, hipMemcpyAsync(overlap + s0 * sz.overlap, drec, (size_t)n * sz.overlap * sizeof(int64_t),
+                                 hipMemcpyDeviceToHost, h->stream));
+        if (sz.steps)
+            HIPCHK(h, hipMemcpyAsync(steps + s0 * sz.steps, drec + (size_t)n * sz.overlap,
+                                     (size_t)n * sz.steps * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (geo)
+        HIPCHK(h, hipMemcpyAsync(geodesic + s0 * sz.geodesic, drec + (size_t)n * (sz.overlap + sz.steps),
+                                 (size_t)n * sz.geodesic * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (temporal)
+        for (int s = 0; s < n; ++s) {
+            int64_t *o = overlap + (s0 + s) * sz.overlap;
+            for (int t = 0; t < T; ++t)
+                for (int u = t + 1; u < T; ++u) o[(size_t)u * T + t] = o[(size_t)t * T + u];
+        }
+    return DLSM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dlsm_gof_dynamic_simulate(dlsm_chain *h, const double *Xs, const double *intercepts, const double *radii,
+                              int S, uint64_t seed, uint32_t first_index, int batch, int64_t *overlap,
+                              int64_t *steps, int64_t *geodesic, uint32_t *bits) {
+    NEED(h, h && Xs && intercepts, "null argument");
+    const bool temporal = overlap != nullptr, geo = geodesic != nullptr;
+    NEED(h, temporal || geo, "overlap and steps, or geodesic, or both must be given");
+    NEED(h, temporal == (steps != nullptr) || h->T == 1, "overlap and steps go together");
+    const bool directed = h->model != DLSM_UNDIRECTED;
+    NEED(h, !directed || radii, "directed models need the radii");
+    NEED(h, S >= 1, "needs at least one sample");
+    NEED(h, batch >= 0, "batch must be >= 0 (0: automatic)");
+    NEED(h, (uint64_t)first_index + (uint64_t)S <= ((uint64_t)1 << 32), "first_index + S must be <= 2^32");
+    int rc = gof_dynamic_check(h, geo);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int T = h->T, N = h->N, D = h->D, W = h->W;
+    const GofDynSizes sz(T, N, temporal, geo);
+    const size_t net_words = (size_t)N * W, nmat = directed ? 2 : 1;
+    const size_t per_sample = (size_t)T * (net_words * nmat * sizeof(uint32_t) + (size_t)N * D * sizeof(double)) +
+                              sz.total() * sizeof(int64_t);
+    int nb = batch > 0 ? batch : (int)std::max<size_t>(1, GOF_SCRATCH_BYTES / per_sample);
+    nb = std::min(nb, S);
+    nb = std::min(nb, std::max(1, 65535 / T));          // networks of a batch: the grid's y extent
+    DevBuf bX, bB, bR, bBits, bS;
+    HIPCHK(h, hipMalloc(&bX.p, (size_t)nb * T * N * D * sizeof(double)));
+    HIPCHK(h, hipMalloc(&bB.p, (size_t)nb * 2 * sizeof(double)));
+    if (directed) HIPCHK(h, hipMalloc(&bR.p, (size_t)nb * N * sizeof(double)));
+    HIPCHK(h, hipMalloc(&bBits.p, (size_t)nb * T * net_words * nmat * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&bS.p, (size_t)nb * sz.total() * sizeof(int64_t)));
+    const unsigned gx = (unsigned)((net_words + 255) / 256);
+    for (int s0 = 0; s0 < S; s0 += nb) {
+        const int n = std::min(nb, S - s0), nets = n * T;
+        HIPCHK(h, hipMemcpyAsync(bX.p, Xs + (size_t)s0 * T * N * D, (size_t)nets * N * D * sizeof(double),
+                                 hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(bB.p, intercepts + 2 * (size_t)s0, (size_t)n * 2 * sizeof(double),
+                                 hipMemcpyHostToDevice, h->stream));
+        if (directed)
+            HIPCHK(h, hipMemcpyAsync(bR.p, radii + (size_t)s0 * N, (size_t)n * N * sizeof(double),
+                                     hipMemcpyHostToDevice, h->stream));
+        DISPATCH_D(h, D, hipLaunchKernelGGL((k_gof_draw<DD>), dim3(gx, nets, (unsigned)nmat), dim3(256), 0,
+                                            h->stream, bX.as<double>(), bB.as<double>(),
+                                            directed ? bR.as<double>() : nullptr, T, N, W, (int)directed,
+                                            seed, first_index + (uint32_t)s0, bBits.as<uint32_t>()));
+        HIPCHK(h, hipGetLastError());
+        const uint32_t *rows = bBits.as<uint32_t>();
+        rc = gof_dynamic_launch(h, rows, directed ? rows + (size_t)nets * net_words : nullptr, n, temporal, geo,
+                                bS.as<int64_t>());
+        if (rc) return rc;
+        if (bits)
+            HIPCHK(h, hipMemcpyAsync(bits + (size_t)s0 * T * net_words, rows,
+                                     (size_t)nets * net_words * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                     h->stream));
+        rc = gof_dynamic_fetch(h, bS.as<int64_t>(), n, (size_t)s0, temporal, geo, overlap, steps, geodesic);
+        if (rc) return rc;
+    }
+    return DLSM_OK;
+}
+
+int dlsm_gof_dynamic_observed(dlsm_chain *h, const uint32_t *bits, int64_t *overlap, int64_t *steps,
+                              int64_t *geodesic) {
+    NEED(h, h && bits, "null argument");
+    const bool temporal = overlap != nullptr, geo = geodesic != nullptr;
+    NEED(h, temporal || geo, "overlap and steps, or geodesic, or both must be given");
+    NEED(h, temporal == (steps != nullptr) || h->T == 1, "overlap and steps go together");
+    int rc = gof_dynamic_check(h, geo);
+    if (rc) return rc;
+    const int T = h->T, N = h->N, W = h->W;
+    const size_t net_words = (size_t)N * W;
+    // the padding bits and the diagonal are zero
+    for (size_t row = 0; row < (size_t)T * N; ++row) {
+        const uint32_t *r = bits + row * W;
+        const int i = (int)(row % N);
+        if ((r[i >> 5] >> (i & 31)) & 1u)
+            FAIL(h, DLSM_E_DATA, "network has a self-loop (t=%d, i=%d)", (int)(row / N), i);
+        for (int w = N >> 5; w < W; ++w) {
+            const int lo = 32 * w;
+            const uint32_t pad = lo >= N ? 0xFFFFFFFFu : ~((1u << (N - lo)) - 1u);
+            if (r[w] & pad) FAIL(h, DLSM_E_DATA, "padding bits beyond column N-1 must be zero");
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const bool directed = h->model != DLSM_UNDIRECTED;
+    const bool need_t = directed && temporal && T > 1;          // only the shared partners read the columns
+    const GofDynSizes sz(T, N, temporal, geo);
+    DevBuf bBits, bT, bS;
+    HIPCHK(h, hipMalloc(&bBits.p, (size_t)T * net_words * sizeof(uint32_t)));
+    if (need_t) HIPCHK(h, hipMalloc(&bT.p, (size_t)T * net_words * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc(&bS.p, sz.total() * sizeof(int64_t)));
+    HIPCHK(h, hipMemcpyAsync(bBits.p, bits, (size_t)T * net_words * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             h->stream));
+    if (need_t) {
+        hipLaunchKernelGGL(k_gof_transpose, dim3((unsigned)((net_words + 255) / 256), T), dim3(256), 0,
+                           h->stream, bBits.as<uint32_t>(), N, W, bT.as<uint32_t>());
+        HIPCHK(h, hipGetLastError());
+    }
+    rc = gof_dynamic_launch(h, bBits.as<uint32_t>(), need_t ? bT.as<uint32_t>() : nullptr, 1, temporal, geo,
+                            bS.as<int64_t>());
+    if (rc) return rc;
+    return gof_dynamic_fetch(h, bS.as<int64_t>(), 1, 0, temporal, geo, overlap, steps, geodesic);
+}
+
+}  // extern "C"

@@ -785,6 +785,58 @@ class Chain(object):
         self._ck(self._L.dlsm_gof_observed(self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(stats)))
         return stats
 
+    def _gof_dynamic_records(self, lead, temporal, geodesic):
+        if not (temporal or geodesic):
+            raise ValueError('at least one of temporal and geodesic must be requested')
+        ov = np.zeros(lead + (self.T, self.T), dtype=np.int64) if temporal else None
+        st = np.zeros(lead + (self.T - 1, 2 * self.N), dtype=np.int64) if temporal else None
+        geo = np.zeros(lead + (self.T, self.N), dtype=np.int64) if geodesic else None
+        return ov, st, geo
+
+    def gof_dynamic_simulate(self, Xs, intercepts, radii=None, seed=0, first_index=0, batch=0, temporal=True,
+                             geodesic=True, want_bits=False):
+        """The statistics over time of the networks ``gof_simulate`` draws for the same arguments, ``seed``
+        and ``first_index``: ``overlap`` (S, T, T), ``steps`` (S, T - 1, 2N) - persist_degree[N] and
+        formed_sp[N] per step t -> t+1 - and ``geodesic`` (S, T, N) int64 (csrc/kernels_gof_dynamic.hpp;
+        layouts in include/dynetlsm_hip.h).  ``temporal=False`` leaves out overlap and steps,
+        ``geodesic=False`` the geodesic distances: those entries are None.  ``want_bits``: also the drawn
+        rows (S, T, N, W) uint32.  Returns (overlap, steps, geodesic[, bits])."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        S = Xs.shape[0]
+        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
+        b = np.asarray(intercepts, dtype=np.float64)
+        if b.ndim == 1 and self.model == UNDIRECTED:
+            b = np.stack([b, np.zeros_like(b)], axis=1)
+        b = _f64(b, (S, 2), 'intercepts')
+        if self.model == UNDIRECTED:
+            r = None
+        else:
+            if radii is None:
+                raise ValueError('directed models need radii')
+            r = _f64(radii, (S, self.N), 'radii')
+        ov, st, geo = self._gof_dynamic_records((S,), temporal, geodesic)
+        W = packed_row_words(self.N)
+        bits = np.zeros((S, self.T, self.N, W), dtype=np.uint32) if want_bits else None
+        self._ck(self._L.dlsm_gof_dynamic_simulate(
+            self._h, _p(Xs), _p(b), _p(r) if r is not None else None, int(S),
+            C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(first_index)), int(batch),
+            _p(ov) if temporal else None, _p(st) if temporal else None, _p(geo) if geodesic else None,
+            bits.ctypes.data_as(_lib.c_u32_p) if want_bits else None))
+        return (ov, st, geo, bits) if want_bits else (ov, st, geo)
+
+    def gof_dynamic_observed(self, bits, temporal=True, geodesic=True):
+        """(overlap (T, T), steps (T - 1, 2N), geodesic (T, N)) int64 of the packed network ``bits``
+        (T, N, W) uint32 (``pack_network``); a family that is switched off is None"""
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        if bits.shape != (self.T, self.N, packed_row_words(self.N)):
+            raise ValueError('bits has shape %s, expected %s'
+                             % (bits.shape, (self.T, self.N, packed_row_words(self.N))))
+        ov, st, geo = self._gof_dynamic_records((), temporal, geodesic)
+        self._ck(self._L.dlsm_gof_dynamic_observed(
+            self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(ov) if temporal else None,
+            _p(st) if temporal else None, _p(geo) if geodesic else None))
+        return ov, st, geo
+
     # -- information criteria (no reference counterpart) ---------------------------------------
     def ic_accumulate(self, bits, Xs, intercepts, radii=None, want_pointwise=False):
         """Pointwise log-likelihood of the packed network ``bits`` (T, N, W) uint32 (``pack_network``)

@@ -402,6 +402,25 @@ int dlsm_gof_simulate(dlsm_chain *h, const double *Xs, const double *intercepts,
  * network `bits` T*N*W uint32 supplied by the caller; stats T*R int64.  A set diagonal or padding
  * bit -> DLSM_E_DATA. */
 int dlsm_gof_observed(dlsm_chain *h, const uint32_t *bits, int64_t *stats);
+/* goodness of fit over time (no reference counterpart): the statistics of the same draws that look
+ * across time steps and beyond two hops.  "Dyad": an unordered pair i < j of an undirected handle, an
+ * arc i -> j of a directed or case-control handle (as `edges` above); all records int64.
+ *   overlap  S*T*T: [t][u] dyads present at both t and u (symmetric; the diagonal is edges[t])
+ *   steps    S*(T-1)*2N, per step t -> t+1: [k] nodes with k ties present at both t and t+1 (directed:
+ *            out-arcs); [N + k] dyads absent at t and present at t+1 with k shared partners at t (the
+ *            partner definition of the record above), k = 0..N-1
+ *   geodesic S*T*N: [k] pairs at shortest-path length k = 1..N-1 (undirected: pairs i < j; directed:
+ *            ordered pairs, paths along the arcs), [0] pairs without a path; N <= 32768, else DLSM_E_LIMIT
+ * overlap and steps go together (steps may be NULL when T = 1); that pair or geodesic may be NULL and
+ * is then not computed, both NULL -> DLSM_E_ARG.  Every other argument, check, the batching and the RNG
+ * indexing are those of dlsm_gof_simulate: the same seed and first_index draw the same networks. */
+int dlsm_gof_dynamic_simulate(dlsm_chain *h, const double *Xs, const double *intercepts, const double *radii,
+                              int S, uint64_t seed, uint32_t first_index, int batch, int64_t *overlap,
+                              int64_t *steps, int64_t *geodesic, uint32_t *bits);
+/* the same records (S = 1) of a packed network `bits` T*N*W uint32 supplied by the caller, validated as
+ * dlsm_gof_observed validates it. */
+int dlsm_gof_dynamic_observed(dlsm_chain *h, const uint32_t *bits, int64_t *overlap, int64_t *steps,
+                              int64_t *geodesic);
 
 /* ---- information criteria (WAIC, DIC) ----------------------------------- */
 /* No reference counterpart.  The pointwise log-likelihood l_s = y eta_s - log(1 + exp(eta_s)) of every
