@@ -16,6 +16,7 @@ from . import model_selection  # noqa
 from .gof import posterior_predictive_check, GofResult  # noqa
 from .ic import information_criteria, compare_information_criteria, ICResult  # noqa
 from .scores import in_sample_scores, ScoreResult  # noqa
+from .convergence import convergence_diagnostics, ConvergenceResult  # noqa
 from . import forecast  # noqa  (the one-step module; calling it is forecast_paths.forecast)
 from .forecast_paths import ForecastResult  # noqa
 
@@ -24,4 +25,5 @@ __all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
            'DynamicNetworkLSM', 'DynamicNetworkHDPLPCM', 'DynamicNetworkLPCM',
            'DirectedCaseControlSampler', 'posterior_predictive_check', 'GofResult',
            'information_criteria', 'compare_information_criteria', 'ICResult',
-           'in_sample_scores', 'ScoreResult', 'forecast', 'ForecastResult']
+           'in_sample_scores', 'ScoreResult', 'convergence_diagnostics', 'ConvergenceResult', 'forecast',
+           'ForecastResult']

@@ -34,6 +34,7 @@
 #include "kernels_gof_dynamic.hpp"
 #include "kernels_ic.hpp"
 #include "kernels_score.hpp"
+#include "kernels_conv.hpp"
 #include "kernels_missing.hpp"
 #include "host_draws.hpp"
 
@@ -2210,6 +2211,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_gof_dynamic.hpp"
 #include "capi_ic.hpp"
 #include "capi_score.hpp"
+#include "capi_conv.hpp"
 #include "capi_forecast_paths.hpp"
 #include "capi_hdp.hpp"
 

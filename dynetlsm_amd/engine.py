@@ -911,6 +911,59 @@ class Chain(object):
             _p(r) if r is not None else None, int(S), counts.ctypes.data_as(_lib.c_u64_p), _p(logloss_sum)))
         return counts, logloss_sum
 
+    # -- convergence of every dyad (no reference counterpart) -----------------------------------
+    def convergence_accumulate(self, Xs, intercepts, radii=None, n_segments=2, seg_len=None, batch_len=None,
+                               rhat_edges=(), ess_edges=(), want_pointwise=False):
+        """Split R-hat and batch-means ESS of the linear predictor of every dyad over the S =
+        ``n_segments * seg_len`` samples ``Xs`` (S, T, N, D), ``intercepts`` (S,) or (S, 2), ``radii``
+        (S, N) (directed and case-control chains): the halves of the chains, segment after segment
+        (csrc/kernels_conv.hpp).  ``batch_len`` defaults to floor(sqrt(seg_len)).  Returns ``hist_rhat``
+        (T, len(rhat_edges) + 1) and ``hist_ess`` (T, len(ess_edges) + 1) uint64 - the bin of a value is
+        the number of edges <= it -, ``node_rhat_max`` (T, N) and ``node_ess_min`` (T, N) over the dyads
+        of each node; ``want_pointwise``: also (T, N, N, 2), (rhat, ess) per dyad (undirected: i < j
+        filled, the rest 0)."""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        S = Xs.shape[0]
+        n_segments = int(n_segments)
+        if seg_len is None:
+            seg_len = S // max(1, n_segments)
+        seg_len = int(seg_len)
+        if n_segments < 2 or n_segments % 2 or seg_len < 2 or n_segments * seg_len != S:
+            raise ValueError('S=%d samples are not n_segments=%d (even, >= 2) segments of seg_len=%d (>= 2)'
+                             % (S, n_segments, seg_len))
+        if batch_len is None:
+            batch_len = int(np.floor(np.sqrt(seg_len)))
+        batch_len = int(batch_len)
+        if not 1 <= batch_len <= seg_len // 2:
+            raise ValueError('batch_len=%d is not between 1 and seg_len // 2 = %d' % (batch_len, seg_len // 2))
+        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
+        b = np.asarray(intercepts, dtype=np.float64)
+        if b.ndim == 1 and self.model == UNDIRECTED:
+            b = np.stack([b, np.zeros_like(b)], axis=1)
+        b = _f64(b, (S, 2), 'intercepts')
+        if self.model == UNDIRECTED:
+            r = None
+        else:
+            if radii is None:
+                raise ValueError('directed models need radii')
+            r = _f64(radii, (S, self.N), 'radii')
+        re_ = np.ascontiguousarray(np.ravel(rhat_edges), dtype=np.float64)
+        ee = np.ascontiguousarray(np.ravel(ess_edges), dtype=np.float64)
+        if re_.size > 16 or ee.size > 16:
+            raise ValueError('at most 16 edges per histogram')
+        hist_rhat = np.zeros((self.T, re_.size + 1), dtype=np.uint64)
+        hist_ess = np.zeros((self.T, ee.size + 1), dtype=np.uint64)
+        node_rhat = np.zeros((self.T, self.N))
+        node_ess = np.zeros((self.T, self.N))
+        pw = np.zeros((self.T, self.N, self.N, 2)) if want_pointwise else None
+        self._ck(self._L.dlsm_convergence_accumulate(
+            self._h, _p(Xs), _p(b), _p(r) if r is not None else None, n_segments, seg_len, batch_len,
+            _p(re_) if re_.size else None, int(re_.size), _p(ee) if ee.size else None, int(ee.size),
+            hist_rhat.ctypes.data_as(_lib.c_u64_p), hist_ess.ctypes.data_as(_lib.c_u64_p), _p(node_rhat),
+            _p(node_ess), _p(pw) if want_pointwise else None))
+        out = (hist_rhat, hist_ess, node_rhat, node_ess)
+        return out + (pw,) if want_pointwise else out
+
     # -- multi-step posterior predictive forecasts (the reference: one step, undirected, on the host) ----
     def forecast_paths(self, X0, intercepts, radii=None, z0=None, trans=None, mu=None, sigma=None, lmbda=None,
                        sigma_sq=0.0, horizon=1, seed=0, first_index=0, batch=0, want_paths=False,

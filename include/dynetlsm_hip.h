@@ -460,6 +460,35 @@ int dlsm_score_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *m
                           const double *intercepts, const double *radii, int S, uint64_t *counts,
                           double *logloss_sum);
 
+/* ---- convergence of every dyad (split R-hat, batch-means ESS) ------------ */
+/* No reference counterpart.  The linear predictor eta_s of every dyad (as dlsm_ic_accumulate forms it: the same
+ * dyads, the same samples Xs S*T*N*D, intercepts S*2, radii S*N or NULL) is invariant to rotation, reflection,
+ * translation and label switching, so its series can be pooled over chains.  The S = n_segments * seg_len samples
+ * are the halves of the chains (n_segments = 2 * chains), segment after segment, each of seg_len samples in
+ * iteration order.  Per dyad, in one pass and without storing the series (Welford's recurrences):
+ *   W = mean over the segments of their variance (ddof 1), B = seg_len * variance of the segment means (ddof 1),
+ *   var+ = (seg_len - 1) / seg_len * W + B / seg_len
+ *   rhat = sqrt(var+ / W)                    (W == 0: 1 if B == 0, else +inf)
+ *   v_bm = batch_len * variance (ddof 1) of the means of all batches: the samples [q batch_len, (q + 1) batch_len)
+ *          of a segment, q < seg_len / batch_len (the tail of a segment enters no batch)
+ *   ess  = S * var+ / v_bm                   (v_bm == 0: S if var+ == 0, else +inf; not capped at S)
+ * Outputs (bin of a value: the number of edges <= it, so +inf falls into the last one):
+ *   hist_rhat      T*(n_rhat_edges+1) uint64: dyads of time step t per bin of rhat_edges
+ *   hist_ess       T*(n_ess_edges+1) uint64: the same for ess over ess_edges
+ *   node_rhat_max  T*N: the largest rhat over the dyads that contain the node (directed: as sender or receiver);
+ *                  0 for a node without a dyad (N = 1)
+ *   node_ess_min   T*N: the smallest ess over the same dyads; +inf for a node without a dyad
+ *   pointwise      NULL or T*N*N*2: (rhat, ess) of dyad (t, i, j); undirected: i < j filled, the rest 0
+ * Only integer atomics are used: the same call returns the same bits.  n_segments odd or < 2, seg_len < 2,
+ * batch_len outside 1..seg_len/2, more than 16 edges -> DLSM_E_ARG; edges that are not finite and ascending, a
+ * radius <= 0 -> DLSM_E_DATA.  All S samples are held on the device at once; if they do not fit ->
+ * DLSM_E_LIMIT, and the message names the largest S that does. */
+int dlsm_convergence_accumulate(dlsm_chain *h, const double *Xs, const double *intercepts, const double *radii,
+                                int n_segments, int seg_len, int batch_len, const double *rhat_edges,
+                                int n_rhat_edges, const double *ess_edges, int n_ess_edges, uint64_t *hist_rhat,
+                                uint64_t *hist_ess, double *node_rhat_max, double *node_ess_min,
+                                double *pointwise);
+
 /* ---- multi-step posterior predictive forecasts --------------------------- */
 /* The reference has only the one-step undirected form (hdp_lpcm.py:555-626, drawn on the host).  One
  * trajectory of H future time steps per sample s, started at the sample's last time step X0 S*N*D:
