@@ -99,8 +99,11 @@ int dlsm_post_trace_label_counts(dlsm_chain *h, int first, int count, int32_t *n
     HIPCHK(h, hipMalloc(&out.p, n * sizeof(int32_t)));
     {
         ProfScope ps(h, DLSM_K_LABELS);
-        hipLaunchKernelGGL(k_post_label_counts, dim3(T, count), dim3(256), 0, h->stream,
-                           h->htr_z + (size_t)first * T * N, N, K, out.as<int32_t>());
+        // (the rows go on the x extent, capped: the kernel strides over what is left)
+        const size_t rows = (size_t)count * T;
+        const unsigned nb = (unsigned)std::min<size_t>(rows, (size_t)1 << 20);
+        hipLaunchKernelGGL(k_post_label_counts, dim3(nb), dim3(256), 0, h->stream,
+                           h->htr_z + (size_t)first * T * N, rows, N, K, out.as<int32_t>());
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));

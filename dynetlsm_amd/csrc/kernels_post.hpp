@@ -142,16 +142,20 @@ __global__ __launch_bounds__(256) void k_post_vi_reduce(const double *__restrict
 // ---- post-loop processing on the device-resident trace (hdp_lpcm.py:1085-1162) ------------------
 // nk[s][t][k] = nodes carrying label k at time t of stored sample s (approx_bic.py:26-51,
 // posterior_vi.py:31-36 and label_utils.py:73-81 all start from these counts)
-__global__ __launch_bounds__(256) void k_post_label_counts(const uint8_t *__restrict__ z, int N, int K,
-                                                           int32_t *__restrict__ nk) {
+// One workgroup per (s, t) row of the trace, the rows walked with the grid's x extent as stride:
+// a chain keeps more samples than the 65535 a y extent can carry.
+__global__ __launch_bounds__(256) void k_post_label_counts(const uint8_t *__restrict__ z, size_t rows,
+                                                           int N, int K, int32_t *__restrict__ nk) {
     __shared__ int hist[256];
-    const int t = blockIdx.x, s = blockIdx.y, T = gridDim.x;
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    const uint8_t *row = z + ((size_t)s * T + t) * N;
-    for (int i = threadIdx.x; i < N; i += 256) atomicAdd(&hist[row[i]], 1);      // integers: order free
-    __syncthreads();
-    if ((int)threadIdx.x < K) nk[((size_t)s * T + t) * K + threadIdx.x] = hist[threadIdx.x];
+    for (size_t r = blockIdx.x; r < rows; r += gridDim.x) {          // r = s T + t
+        hist[threadIdx.x] = 0;
+        __syncthreads();
+        const uint8_t *row = z + r * N;
+        for (int i = threadIdx.x; i < N; i += 256) atomicAdd(&hist[row[i]], 1);  // integers: order free
+        __syncthreads();
+        if ((int)threadIdx.x < K) nk[r * K + threadIdx.x] = hist[threadIdx.x];
+        __syncthreads();                                             // hist is cleared for the next row
+    }
 }
 
 // out[r] = sum_j cooc[r][j], one wavefront per row, fixed order
