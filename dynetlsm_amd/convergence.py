@@ -30,8 +30,7 @@ largest rhat and the smallest ess over the dyads the node is part of.
 """
 import numpy as np
 
-from .engine import Chain
-from .ic import _sample_rows, _two_intercepts
+from ._trace import model_chain, sample_rows, trace_samples
 
 __all__ = ['convergence_diagnostics', 'ConvergenceResult', 'split_segments', 'series_rhat', 'series_ess']
 
@@ -205,7 +204,7 @@ def convergence_diagnostics(models, n_samples=None, pointwise=False, rhat_edges=
         models = [models]
     re_ = _check_edges('rhat_edges', rhat_edges)
     ee = _check_edges('ess_edges', ess_edges)
-    ids = [_sample_rows(m, n_samples) for m in models]
+    ids = [sample_rows(m, n_samples) for m in models]
     first = models[0]
     for m, i in zip(models[1:], ids[1:]):
         if type(m) is not type(first):
@@ -226,15 +225,11 @@ def convergence_diagnostics(models, n_samples=None, pointwise=False, rhat_edges=
     C_ = len(models)
     directed = bool(first.is_directed)
 
-    def rows(a, i):                           # the two halves of a chain's rows
-        return np.asarray(a)[i[:2 * h]]
-
-    Xs = np.ascontiguousarray(np.concatenate([rows(m.Xs_, i) for m, i in zip(models, ids)]), dtype=np.float64)
+    # the two halves of every chain's rows, chain after chain
+    parts = [trace_samples(m, i[:2 * h]) for m, i in zip(models, ids)]
+    Xs, ic = (np.ascontiguousarray(np.concatenate([p[k] for p in parts])) for k in (0, 1))
+    radii = np.concatenate([p[2] for p in parts]) if directed else None
     S, T, N, D = Xs.shape
-    ic = np.concatenate([_two_intercepts(rows(np.asarray(m.intercepts_, dtype=np.float64), i))
-                         for m, i in zip(models, ids)])
-    radii = (np.concatenate([rows(np.asarray(m.radiis_, dtype=np.float64), i) for m, i in zip(models, ids)])
-             if directed else None)
     scalars = {}
     traces = [_scalar_traces(m) for m in models]
     for name in traces[0]:
@@ -242,15 +237,8 @@ def convergence_diagnostics(models, n_samples=None, pointwise=False, rhat_edges=
             q = split_segments(np.stack([tr[name][i] for tr, i in zip(traces, ids)]))
             scalars[name] = (series_rhat(q), series_ess(q, b))
 
-    chain = first.__dict__.get('chain_')
-    own = chain is None or getattr(chain, '_h', None) is None
-    if own:
-        chain = Chain(T, N, D, 'directed' if directed else 'undirected', device=getattr(first, 'device', 0))
-    try:
+    with model_chain(first, T, N, D, directed) as chain:
         out = chain.convergence_accumulate(Xs, ic, radii, n_segments=2 * C_, seg_len=h, batch_len=b,
                                            rhat_edges=re_, ess_edges=ee, want_pointwise=pointwise)
-    finally:
-        if own:
-            chain.close()
     return ConvergenceResult(C_, h, b, ids if len(ids) > 1 else ids[0], re_, ee, out[0], out[1], out[2], out[3],
                              directed, out[4] if pointwise else None, scalars)

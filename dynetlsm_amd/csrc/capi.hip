@@ -32,6 +32,7 @@
 #include "kernels_forecast_paths.hpp"
 #include "kernels_gof.hpp"
 #include "kernels_gof_dynamic.hpp"
+#include "kernels_dyad_pass.hpp"
 #include "kernels_ic.hpp"
 #include "kernels_score.hpp"
 #include "kernels_conv.hpp"
@@ -2207,6 +2208,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_init.hpp"
 #include "capi_post.hpp"
 #include "capi_forecast.hpp"
+#include "capi_samples.hpp"
 #include "capi_gof.hpp"
 #include "capi_gof_dynamic.hpp"
 #include "capi_ic.hpp"

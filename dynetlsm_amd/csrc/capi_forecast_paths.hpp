@@ -6,17 +6,6 @@ namespace {
 
 constexpr size_t FP_SCRATCH_BYTES = (size_t)256 << 20;    // device scratch of one batch (auto batching)
 
-template <int D>
-void fp_mean_launch(dlsm_chain *h, bool directed, dim3 grid, const double *Xh, const double *ic,
-                    const double *radii, int ns, int first, int last, int S, double *sum) {
-    if (directed)
-        hipLaunchKernelGGL((k_forecast_paths_mean<D, true>), grid, dim3(256), 0, h->stream, Xh, ic, radii, ns,
-                           h->N, first, last, S, sum);
-    else
-        hipLaunchKernelGGL((k_forecast_paths_mean<D, false>), grid, dim3(256), 0, h->stream, Xh, ic, radii, ns,
-                           h->N, first, last, S, sum);
-}
-
 }  // namespace
 
 extern "C" {
@@ -57,9 +46,7 @@ int dlsm_forecast_paths(dlsm_chain *h, const double *X0, const double *intercept
         NEED(h, sigma_sq >= 0.0 && std::isfinite(sigma_sq), "sigma_sq must be >= 0");
         NEED(h, !labels, "the random walk has no labels");
     }
-    if (directed)
-        for (size_t k = 0; k < (size_t)S * N; ++k)
-            if (!(radii[k] > 0.0)) FAIL(h, DLSM_E_DATA, "radii must be positive (sample %zu, node %zu)", k / N, k % N);
+    if (int rc = check_radii_positive(h, radii, S)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     // samples per batch: the draws of a batch ([H][nb][N][D] and the labels) within FP_SCRATCH_BYTES
     const size_t per_sample = (size_t)H * N * (D * sizeof(double) + (mixture ? sizeof(int32_t) : 0)) +
@@ -119,9 +106,9 @@ int dlsm_forecast_paths(dlsm_chain *h, const double *X0, const double *intercept
                                                 N, seed, first_index + (uint32_t)s0, bP.as<double>(),
                                                 bLab.as<int32_t>()));
             HIPCHK(h, hipGetLastError());
-            DISPATCH_D(h, D, fp_mean_launch<DD>(h, directed, dim3(nt, nt, (unsigned)H), bP.as<double>(),
-                                                bB.as<double>(), directed ? bR.as<double>() : nullptr, n,
-                                                (int)(s0 == 0), (int)(s0 + n == S), S, bSum.as<double>()));
+            DISPATCH_D(h, D, LAUNCH_DIR(directed, k_forecast_paths_mean, dim3(nt, nt, (unsigned)H), dim3(256),
+                                        h->stream, bP.as<double>(), bB.as<double>(), bR.as<double>(), n, N,
+                                        (int)(s0 == 0), (int)(s0 + n == S), S, bSum.as<double>()));
             HIPCHK(h, hipGetLastError());
         }
         if (paths)

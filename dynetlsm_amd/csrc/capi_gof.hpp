@@ -1,5 +1,5 @@
 // C-ABI of the posterior predictive goodness-of-fit check (kernels_gof.hpp; included by capi.hip after
-// capi_forecast.hpp).  The reference has no counterpart.
+// capi_samples.hpp).  The reference has no counterpart.
 #pragma once
 
 namespace {
@@ -85,18 +85,7 @@ int dlsm_gof_observed(dlsm_chain *h, const uint32_t *bits, int64_t *stats) {
     NEED(h, h && bits && stats, "null argument");
     const int T = h->T, N = h->N, W = h->W;
     const size_t R = 2 + 3 * (size_t)N, net_words = (size_t)N * W;
-    // the padding bits and the diagonal are zero
-    for (size_t row = 0; row < (size_t)T * N; ++row) {
-        const uint32_t *r = bits + row * W;
-        const int i = (int)(row % N);
-        if ((r[i >> 5] >> (i & 31)) & 1u)
-            FAIL(h, DLSM_E_DATA, "network has a self-loop (t=%d, i=%d)", (int)(row / N), i);
-        for (int w = N >> 5; w < W; ++w) {
-            const int lo = 32 * w;
-            const uint32_t pad = lo >= N ? 0xFFFFFFFFu : ~((1u << (N - lo)) - 1u);
-            if (r[w] & pad) FAIL(h, DLSM_E_DATA, "padding bits beyond column N-1 must be zero");
-        }
-    }
+    if (int rc = check_packed_network(h, bits)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const bool directed = h->model != DLSM_UNDIRECTED;
     DevBuf bBits, bT, bS;

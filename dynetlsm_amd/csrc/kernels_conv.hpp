@@ -1,6 +1,6 @@
 // Convergence of every dyad (no reference counterpart): split R-hat and a batch-means effective sample size of
 // the linear predictor eta_s of dyad (t, i, j) over S = M h samples, M segments (the two halves of every chain)
-// of h samples each, segment after segment.  eta (as k_ic_accumulate, kernels_ic.hpp) is invariant to rotation,
+// of h samples each, segment after segment.  eta (conv_eta, kernels_dyad_pass.hpp) is invariant to rotation,
 // reflection, translation and label switching, so chains pool without alignment.  Per dyad, in eight float64
 // registers and without storing the series:
 //
@@ -25,14 +25,14 @@
 //   pointwise NULL or [T][N][N][2] = (rhat, ess)
 // Only integer atomics: the same bits on every call.
 //
-// Tiling, LDS staging of the samples and the tile list are those of k_ic_accumulate (IcPlan, IcStage,
-// ic_stage_load); the network itself is not read.
+// Tiling, LDS staging of the samples and the tile list are the shared ones of a pass over posterior samples
+// (kernels_dyad_pass.hpp), eta its conv_eta; the network itself is not read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device_common.hpp"
-#include "kernels_ic.hpp"
+#include "kernels_dyad_pass.hpp"
 
 namespace dlsm {
 
@@ -64,28 +64,6 @@ __device__ __forceinline__ double conv_wave_min(double v) {
     v = fmin(v, dpp_move<0x141>(v));
     v = fmin(v, dpp_move<0x140>(v));
     return fmin(fmin(lane_value(v, 0), lane_value(v, 16)), fmin(lane_value(v, 32), lane_value(v, 48)));
-}
-
-// eta of one dyad, every operation rounded on its own (no fused multiply-add): bit for bit what float64 numpy
-// gives for the definition.  Where a segment's variance is small against the predictor, rhat amplifies a last-bit
-// difference in eta by |eta| / |eta_s - eta_s'|; measured at h = 2, a fused sum of squares moved an rhat of
-// 33 by 250 ulp.
-template <int D, bool DIR>
-__device__ __forceinline__ double conv_eta(const double *xi, const double (&xj)[D], double b0, double b1, double rj,
-                                           double ri) {
-#pragma clang fp contract(off)
-    double s2 = 0.0;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const double df = xi[d] - xj[d];
-        s2 = s2 + df * df;
-    }
-    const double dist = sqrt(s2);
-    if (DIR) {
-        const double in = b0 * (1.0 - dist / rj), out = b1 * (1.0 - dist / ri);
-        return in + out;
-    }
-    return b0 - dist;
 }
 
 // Xs [S][T][N][D], ic [S][2], radii [S][N] (DIR), S = M h; tiles [n_tiles] = (row block, column block);
@@ -127,41 +105,21 @@ __global__ __launch_bounds__(IC_NT) void k_conv_accumulate(
 #pragma unroll
         for (int k = 0; k < DPT; ++k)
             mean[k] = m2[k] = sw[k] = mm[k] = mm2[k] = bs[k] = bm[k] = bm2[k] = 0.0;
-        // sample 0 into buffer 0
-        {
-            const double *X0 = Xs + (size_t)t * N * D;
-#pragma unroll
-            for (int p = 0; p < PT; ++p) {
-                const int e = tid + p * IC_NT;
-                if (e < St::N) stage[0][e] = ic_stage_load<D, DIR>(X0, ic, radii, N, i0, j0, e);
-            }
-        }
+        dyad_stage_first<D, DIR>(stage[0], Xs, ic, radii, t, N, i0, j0, tid);
         __syncthreads();
         int pos = 0, bpos = 0, seg = 0, nb = 0;               // s % h, (s % h) % b, s / h, batches so far
         for (int s = 0; s < S; ++s) {
             const int cur = s & 1;
             const double *sb = stage[cur];
-            // the next sample's block, in flight under this sample's arithmetic
-            double pre[PT];
-            if (s + 1 < S) {
-                const double *Xn = Xs + ((size_t)(s + 1) * T + t) * N * D;
-                const double *icn = ic + 2 * (size_t)(s + 1);
-                const double *rn = DIR ? radii + (size_t)(s + 1) * N : nullptr;
-#pragma unroll
-                for (int p = 0; p < PT; ++p)
-                    pre[p] = ic_stage_load<D, DIR>(Xn, icn, rn, N, i0, j0, tid + p * IC_NT);
-            }
-            double xj[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) xj[d] = sb[St::XJ + lane * D + d];
-            const double b0 = sb[St::B], b1 = sb[St::B + 1];
-            const double rj = DIR ? sb[St::RJ + lane] : 1.0;
+            double pre[PT];           // the next sample's block, in flight under this sample's arithmetic
+            if (s + 1 < S) dyad_stage_prefetch<D, DIR>(pre, Xs, ic, radii, s + 1, T, t, N, i0, j0, tid);
+            const DyadColumn<D> col = dyad_column<D, DIR>(sb, lane);
             const double inv_n = 1.0 / (double)(pos + 1);
             const bool batch_first = bpos == 0;
 #pragma unroll
             for (int k = 0; k < DPT; ++k) {
                 const int row = 4 * k + wv;
-                const double eta = conv_eta<D, DIR>(sb + St::XI + row * D, xj, b0, b1, rj,
+                const double eta = conv_eta<D, DIR>(sb + St::XI + row * D, col.xj, col.b0, col.b1, col.rj,
                                                     DIR ? sb[St::RI + row] : 1.0);
                 const double delta = eta - mean[k];
                 mean[k] = fma(delta, inv_n, mean[k]);
@@ -195,13 +153,7 @@ __global__ __launch_bounds__(IC_NT) void k_conv_accumulate(
             } else {
                 ++pos;
             }
-            if (s + 1 < S) {
-#pragma unroll
-                for (int p = 0; p < PT; ++p) {
-                    const int e = tid + p * IC_NT;
-                    if (e < St::N) stage[cur ^ 1][e] = pre[p];
-                }
-            }
+            if (s + 1 < S) dyad_stage_commit<D, DIR>(stage[cur ^ 1], pre, tid);
             __syncthreads();
         }
         // the tile's dyads: rhat and ess; a dyad that does not exist holds the identities 0 and +inf

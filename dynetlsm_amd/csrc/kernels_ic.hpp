@@ -7,14 +7,8 @@
 // sum r = sum_s exp(l_s - m) of a streaming log-sum-exp, and Welford's mean and M2 - and never stores
 // l_s.  At the end lppd = m + log(r / S), var = M2 / (S - 1) (0 for S = 1), elpd = lppd - var.
 //
-// Work: a workgroup of 256 threads owns tiles of IcPlan<D>::TI x 64 dyads of one time step (rows x
-// columns; undirected: only tiles that hold a dyad i < j).  Lane = column, wavefront + 4 k = row:
-// IcPlan<D>::DPT dyads per thread.  Per sample the tile's two position blocks (directed: two radii blocks
-// as well) and the intercepts are staged in LDS, double buffered: sample s + 1 is loaded into registers
-// before the arithmetic of sample s and stored to the other buffer after it, one barrier per sample.
-// The arithmetic is the compiler's correctly rounded sqrt and division and the library's exp / log1p:
-// the outputs are compared with numpy at a few ulp, which the engine's lean sqrt (35 ulp on a distance,
-// device_common.hpp) does not give.
+// Work: the tiles, the LDS staging of the samples and eta are the shared ones of a pass over posterior samples
+// (kernels_dyad_pass.hpp); the library's exp / log1p give the outputs at a few ulp of numpy.
 //
 // Sums leave the kernel as per-workgroup partials, added in a fixed order (DPP butterflies, the four
 // wavefronts in index order, a workgroup's tiles in index order) and summed over the workgroups in index
@@ -24,38 +18,11 @@
 #include <stdint.h>
 
 #include "device_common.hpp"
+#include "kernels_dyad_pass.hpp"
 
 namespace dlsm {
 
-constexpr int IC_TJ = 64;                   // columns of a tile: one per lane
-constexpr int IC_NT = 256;                  // threads of a workgroup
-// dyads per thread: 4 accumulators each (8 registers) next to D coordinates of the column
-template <int D> struct IcPlan { static constexpr int DPT = D <= 4 ? 8 : 4, TI = 4 * DPT; };
-
 constexpr int IC_NTOT = 5;                  // sum lppd, sum var, sum mean, sum elpd^2, dyads
-
-// doubles staged per sample: rows' positions, columns' positions, rows' radii, columns' radii, intercepts
-template <int D, bool DIR> struct IcStage {
-    static constexpr int TI = IcPlan<D>::TI;
-    static constexpr int XI = 0, XJ = TI * D, RI = XJ + IC_TJ * D, RJ = RI + (DIR ? TI : 0),
-                         B = RJ + (DIR ? IC_TJ : 0), N = B + 2;
-    static constexpr int PER_THREAD = (N + IC_NT - 1) / IC_NT;
-};
-
-// element e of the staging block of one sample (X [N][D] of its time step, ic [2], rad [N]) for the tile
-// of rows i0.., columns j0..; rows and columns beyond N read as position 0 and radius 1 (their dyads are
-// masked out), e >= IcStage::N as 0
-template <int D, bool DIR>
-__device__ __forceinline__ double ic_stage_load(const double *__restrict__ X, const double *__restrict__ ic,
-                                                const double *__restrict__ rad, int N, int i0, int j0, int e) {
-    typedef IcStage<D, DIR> St;
-    if (e < St::XJ) return (i0 * D + e < N * D) ? X[(size_t)i0 * D + e] : 0.0;
-    if (e < St::RI) { e -= St::XJ; return (j0 * D + e < N * D) ? X[(size_t)j0 * D + e] : 0.0; }
-    if (DIR && e < St::RJ) { e -= St::RI; return (i0 + e < N) ? rad[i0 + e] : 1.0; }
-    if (DIR && e < St::B) { e -= St::RJ; return (j0 + e < N) ? rad[j0 + e] : 1.0; }
-    if (e < St::N) return ic[e - St::B];
-    return 0.0;
-}
 
 // Xs [S][T][N][D], ic [S][2], radii [S][N] (DIR); bits [T][N][W]; tiles [n_tiles] = (row block, column
 // block); workgroup g = blockIdx.x takes tiles g L .. g L + L - 1 of time step blockIdx.y.
@@ -78,63 +45,25 @@ __global__ __launch_bounds__(IC_NT) void k_ic_accumulate(
     for (int q = q0; q < q1; ++q) {
         const int i0 = tiles[q].x * TI, j0 = tiles[q].y * IC_TJ;
         const int j = j0 + lane;
-        // the tile's dyads of this thread: which exist, and the network's bits
-        uint32_t valid = 0, ybits = 0;
-#pragma unroll
-        for (int k = 0; k < DPT; ++k) {
-            const int i = i0 + 4 * k + wv;
-            const bool ok = i < N && j < N && (DIR ? i != j : i < j);
-            if (ok) {
-                valid |= 1u << k;
-                ybits |= ((bits[((size_t)t * N + i) * W + (j >> 5)] >> (j & 31)) & 1u) << k;
-            }
-        }
+        uint32_t valid, ybits;        // the tile's dyads of this thread: which exist, and the network's bits
+        dyad_tile_bits<D, DIR>(bits, nullptr, t, N, W, i0, j, wv, valid, ybits);
         // m = -inf makes the first sample an ordinary update: r = 0 * e^-inf + 1, mean = l, M2 = 0
         double m[DPT], r[DPT], mean[DPT], m2[DPT];
 #pragma unroll
         for (int k = 0; k < DPT; ++k) { m[k] = -__builtin_inf(); r[k] = 0.0; mean[k] = 0.0; m2[k] = 0.0; }
-        // sample 0 into buffer 0
-        {
-            const double *X0 = Xs + (size_t)t * N * D;
-#pragma unroll
-            for (int p = 0; p < PT; ++p) {
-                const int e = tid + p * IC_NT;
-                if (e < St::N) stage[0][e] = ic_stage_load<D, DIR>(X0, ic, radii, N, i0, j0, e);
-            }
-        }
+        dyad_stage_first<D, DIR>(stage[0], Xs, ic, radii, t, N, i0, j0, tid);
         __syncthreads();
         for (int s = 0; s < S; ++s) {
             const int cur = s & 1;
             const double *sb = stage[cur];
-            // the next sample's block, in flight under this sample's arithmetic
-            double pre[PT];
-            if (s + 1 < S) {
-                const double *Xn = Xs + ((size_t)(s + 1) * T + t) * N * D;
-                const double *icn = ic + 2 * (size_t)(s + 1);
-                const double *rn = DIR ? radii + (size_t)(s + 1) * N : nullptr;
-#pragma unroll
-                for (int p = 0; p < PT; ++p)
-                    pre[p] = ic_stage_load<D, DIR>(Xn, icn, rn, N, i0, j0, tid + p * IC_NT);
-            }
-            double xj[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) xj[d] = sb[St::XJ + lane * D + d];
-            const double b0 = sb[St::B], b1 = sb[St::B + 1];
-            const double rj = DIR ? sb[St::RJ + lane] : 1.0;
+            double pre[PT];           // the next sample's block, in flight under this sample's arithmetic
+            if (s + 1 < S) dyad_stage_prefetch<D, DIR>(pre, Xs, ic, radii, s + 1, T, t, N, i0, j0, tid);
+            const DyadColumn<D> col = dyad_column<D, DIR>(sb, lane);
             const double inv_n = 1.0 / (double)(s + 1);
             double lsum = 0.0;
 #pragma unroll
             for (int k = 0; k < DPT; ++k) {
-                const int row = 4 * k + wv;
-                double s2 = 0.0;
-#pragma unroll
-                for (int d = 0; d < D; ++d) {
-                    const double df = sb[St::XI + row * D + d] - xj[d];
-                    s2 += df * df;
-                }
-                const double dist = sqrt(s2);
-                const double eta = DIR ? b0 * (1.0 - dist / rj) + b1 * (1.0 - dist / sb[St::RI + row])
-                                       : b0 - dist;
+                const double eta = dyad_eta<D, DIR>(sb, 4 * k + wv, col);
                 // y eta - log(1 + e^eta) = y eta - max(eta, 0) - log1p(e^-|eta|): finite for any finite eta
                 const double y = (double)((ybits >> k) & 1u);
                 const double l = y * eta - (fmax(eta, 0.0) + log1p(exp(-fabs(eta))));
@@ -149,13 +78,7 @@ __global__ __launch_bounds__(IC_NT) void k_ic_accumulate(
             }
             lsum = wave_sum_all(lsum);
             if (lane == 0) red[cur][wv] = lsum;
-            if (s + 1 < S) {
-#pragma unroll
-                for (int p = 0; p < PT; ++p) {
-                    const int e = tid + p * IC_NT;
-                    if (e < St::N) stage[cur ^ 1][e] = pre[p];
-                }
-            }
+            if (s + 1 < S) dyad_stage_commit<D, DIR>(stage[cur ^ 1], pre, tid);
             __syncthreads();
             if (tid == 0) {
                 const double v = (red[cur][0] + red[cur][1]) + (red[cur][2] + red[cur][3]);

@@ -1,6 +1,6 @@
 // In-sample scores (no reference counterpart): the AUC and the log-loss of the posterior-mean edge probability
 //
-//     pbar(t, i, j) = (1 / S) sum_s expit(eta_s),      eta as k_ic_accumulate (kernels_ic.hpp)
+//     pbar(t, i, j) = (1 / S) sum_s expit(eta_s),      eta as dyad_eta (kernels_dyad_pass.hpp)
 //
 // over all scored dyads, without storing or sorting them.  A dyad's rank key is the top 24 bits of (float)pbar,
 // clamped from below: key = max(bits(f) >> 8, SCORE_KEY_LO) - 2^15 bins per octave of pbar, every pbar <= 2^-63
@@ -17,14 +17,14 @@
 // finite for any finite eta, one exp for the probability and one for the rescaling.  The terms leave the kernel
 // as per-workgroup partials added in a fixed order (kernels_ic.hpp), so the sums are the same bits on every call.
 //
-// Tiling, LDS staging of the samples and the bit-packed network reads are those of k_ic_accumulate (IcPlan,
-// IcStage, ic_stage_load).
+// Tiling, LDS staging of the samples, the bit-packed network reads and eta are the shared ones of a pass over
+// posterior samples (kernels_dyad_pass.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device_common.hpp"
-#include "kernels_ic.hpp"
+#include "kernels_dyad_pass.hpp"
 
 namespace dlsm {
 
@@ -85,66 +85,23 @@ __global__ __launch_bounds__(IC_NT) void k_score_accumulate(
     for (int q = q0; q < q1; ++q) {
         const int i0 = tiles[q].x * TI, j0 = tiles[q].y * IC_TJ;
         const int j = j0 + lane;
-        // the tile's dyads of this thread: which are scored, and the network's bits
-        uint32_t valid = 0, ybits = 0;
-#pragma unroll
-        for (int k = 0; k < DPT; ++k) {
-            const int i = i0 + 4 * k + wv;
-            bool ok = i < N && j < N && (DIR ? i != j : i < j);
-            if (ok && mask) {
-                uint32_t mb = mask[((size_t)t * N + i) * W + (j >> 5)] >> (j & 31);
-                if (!DIR) mb |= mask[((size_t)t * N + j) * W + (i >> 5)] >> (i & 31);
-                ok = !(mb & 1u);
-            }
-            if (ok) {
-                valid |= 1u << k;
-                ybits |= ((bits[((size_t)t * N + i) * W + (j >> 5)] >> (j & 31)) & 1u) << k;
-            }
-        }
+        uint32_t valid, ybits;        // the tile's dyads of this thread: which are scored, and the network's bits
+        dyad_tile_bits<D, DIR>(bits, mask, t, N, W, i0, j, wv, valid, ybits);
         // m = -inf makes the first sample an ordinary update: r = 0 * e^-inf + w
         double psum[DPT], m[DPT], r[DPT];
 #pragma unroll
         for (int k = 0; k < DPT; ++k) { psum[k] = 0.0; m[k] = -__builtin_inf(); r[k] = 0.0; }
-        // sample 0 into buffer 0
-        {
-            const double *X0 = Xs + (size_t)t * N * D;
-#pragma unroll
-            for (int p = 0; p < PT; ++p) {
-                const int e = tid + p * IC_NT;
-                if (e < St::N) stage[0][e] = ic_stage_load<D, DIR>(X0, ic, radii, N, i0, j0, e);
-            }
-        }
+        dyad_stage_first<D, DIR>(stage[0], Xs, ic, radii, t, N, i0, j0, tid);
         __syncthreads();
         for (int s = 0; s < S; ++s) {
             const int cur = s & 1;
             const double *sb = stage[cur];
-            // the next sample's block, in flight under this sample's arithmetic
-            double pre[PT];
-            if (s + 1 < S) {
-                const double *Xn = Xs + ((size_t)(s + 1) * T + t) * N * D;
-                const double *icn = ic + 2 * (size_t)(s + 1);
-                const double *rn = DIR ? radii + (size_t)(s + 1) * N : nullptr;
-#pragma unroll
-                for (int p = 0; p < PT; ++p)
-                    pre[p] = ic_stage_load<D, DIR>(Xn, icn, rn, N, i0, j0, tid + p * IC_NT);
-            }
-            double xj[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) xj[d] = sb[St::XJ + lane * D + d];
-            const double b0 = sb[St::B], b1 = sb[St::B + 1];
-            const double rj = DIR ? sb[St::RJ + lane] : 1.0;
+            double pre[PT];           // the next sample's block, in flight under this sample's arithmetic
+            if (s + 1 < S) dyad_stage_prefetch<D, DIR>(pre, Xs, ic, radii, s + 1, T, t, N, i0, j0, tid);
+            const DyadColumn<D> col = dyad_column<D, DIR>(sb, lane);
 #pragma unroll
             for (int k = 0; k < DPT; ++k) {
-                const int row = 4 * k + wv;
-                double s2 = 0.0;
-#pragma unroll
-                for (int d = 0; d < D; ++d) {
-                    const double df = sb[St::XI + row * D + d] - xj[d];
-                    s2 += df * df;
-                }
-                const double dist = sqrt(s2);
-                const double eta = DIR ? b0 * (1.0 - dist / rj) + b1 * (1.0 - dist / sb[St::RI + row])
-                                       : b0 - dist;
+                const double eta = dyad_eta<D, DIR>(sb, 4 * k + wv, col);
                 // expit(eta) = w (eta >= 0) or e w, with e = exp(-|eta|) <= 1: no overflow, no cancellation
                 const double e = exp(-fabs(eta));
                 const double w = 1.0 / (1.0 + e);
@@ -156,13 +113,7 @@ __global__ __launch_bounds__(IC_NT) void k_score_accumulate(
                 r[k] = da > 0.0 ? fma(r[k], ex, w) : fma(w, ex, r[k]);
                 m[k] = fmax(m[k], a);
             }
-            if (s + 1 < S) {
-#pragma unroll
-                for (int p = 0; p < PT; ++p) {
-                    const int e = tid + p * IC_NT;
-                    if (e < St::N) stage[cur ^ 1][e] = pre[p];
-                }
-            }
+            if (s + 1 < S) dyad_stage_commit<D, DIR>(stage[cur ^ 1], pre, tid);
             __syncthreads();
         }
         // the tile's dyads: the key into the histogram, the log-loss term into the sum

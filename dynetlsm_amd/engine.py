@@ -742,6 +742,41 @@ class Chain(object):
         self._ck(self._L.dlsm_forecast_marginal(self._h, _p(x), _p(W), _p(b), S, _p(out)))
         return out
 
+    # -- the arguments the passes over posterior samples share -------------------------------
+    def _samples(self, Xs, lead_shape, name, min_samples=1):
+        """``Xs`` as contiguous float64 (S,) + ``lead_shape``, and S"""
+        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
+        S = Xs.shape[0]
+        if S < min_samples:
+            raise ValueError('needs at least one sample')
+        return _f64(Xs, (S,) + tuple(lead_shape), name), S
+
+    def _intercepts_radii(self, intercepts, radii, S):
+        """``intercepts`` (S,) (undirected chains) or (S, 2) as (S, 2); ``radii`` (S, N), which directed
+        chains need (None for undirected ones)"""
+        b = np.asarray(intercepts, dtype=np.float64)
+        if b.ndim == 1 and self.model == UNDIRECTED:
+            b = np.stack([b, np.zeros_like(b)], axis=1)
+        b = _f64(b, (S, 2), 'intercepts')
+        if self.model == UNDIRECTED:
+            return b, None
+        if radii is None:
+            raise ValueError('directed models need radii')
+        return b, _f64(radii, (S, self.N), 'radii')
+
+    def _sample_args(self, Xs, intercepts, radii, min_samples=1):
+        """(Xs (S, T, N, D), intercepts (S, 2), radii (S, N) or None, S) of S posterior samples"""
+        Xs, S = self._samples(Xs, (self.T, self.N, self.D), 'Xs', min_samples)
+        return (Xs,) + self._intercepts_radii(intercepts, radii, S) + (S,)
+
+    def _packed(self, bits, name):
+        """a packed network (``pack_network``) as contiguous uint32 (T, N, W)"""
+        shape = (self.T, self.N, packed_row_words(self.N))
+        bits = np.ascontiguousarray(bits, dtype=np.uint32)
+        if bits.shape != shape:
+            raise ValueError('%s has shape %s, expected %s' % (name, bits.shape, shape))
+        return bits
+
     # -- posterior predictive goodness of fit (no reference counterpart) ----------------------
     def gof_record_length(self):
         """int64 entries of one statistics record: edges, mutual, deg_out[N], deg_in[N], esp[N]"""
@@ -753,19 +788,7 @@ class Chain(object):
         Sample s uses RNG index ``first_index + s``: results do not depend on how the samples are split
         across calls or on ``batch`` (samples per device batch, 0: automatic).  ``want_bits``: also the
         drawn rows (S, T, N, W) uint32, bit j % 32 of word j // 32 of row i = Y[t, i, j]."""
-        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
-        S = Xs.shape[0]
-        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
-        b = np.asarray(intercepts, dtype=np.float64)
-        if b.ndim == 1 and self.model == UNDIRECTED:
-            b = np.stack([b, np.zeros_like(b)], axis=1)
-        b = _f64(b, (S, 2), 'intercepts')
-        if self.model == UNDIRECTED:
-            r = None
-        else:
-            if radii is None:
-                raise ValueError('directed models need radii')
-            r = _f64(radii, (S, self.N), 'radii')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii, min_samples=0)
         stats = np.zeros((S, self.T, self.gof_record_length()), dtype=np.int64)
         W = packed_row_words(self.N)
         bits = np.zeros((S, self.T, self.N, W), dtype=np.uint32) if want_bits else None
@@ -777,10 +800,7 @@ class Chain(object):
 
     def gof_observed(self, bits):
         """statistics (T, R) int64 of the packed network ``bits`` (T, N, W) uint32 (``pack_network``)"""
-        bits = np.ascontiguousarray(bits, dtype=np.uint32)
-        if bits.shape != (self.T, self.N, packed_row_words(self.N)):
-            raise ValueError('bits has shape %s, expected %s'
-                             % (bits.shape, (self.T, self.N, packed_row_words(self.N))))
+        bits = self._packed(bits, 'bits')
         stats = np.zeros((self.T, self.gof_record_length()), dtype=np.int64)
         self._ck(self._L.dlsm_gof_observed(self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(stats)))
         return stats
@@ -801,19 +821,7 @@ class Chain(object):
         layouts in include/dynetlsm_hip.h).  ``temporal=False`` leaves out overlap and steps,
         ``geodesic=False`` the geodesic distances: those entries are None.  ``want_bits``: also the drawn
         rows (S, T, N, W) uint32.  Returns (overlap, steps, geodesic[, bits])."""
-        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
-        S = Xs.shape[0]
-        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
-        b = np.asarray(intercepts, dtype=np.float64)
-        if b.ndim == 1 and self.model == UNDIRECTED:
-            b = np.stack([b, np.zeros_like(b)], axis=1)
-        b = _f64(b, (S, 2), 'intercepts')
-        if self.model == UNDIRECTED:
-            r = None
-        else:
-            if radii is None:
-                raise ValueError('directed models need radii')
-            r = _f64(radii, (S, self.N), 'radii')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii, min_samples=0)
         ov, st, geo = self._gof_dynamic_records((S,), temporal, geodesic)
         W = packed_row_words(self.N)
         bits = np.zeros((S, self.T, self.N, W), dtype=np.uint32) if want_bits else None
@@ -827,10 +835,7 @@ class Chain(object):
     def gof_dynamic_observed(self, bits, temporal=True, geodesic=True):
         """(overlap (T, T), steps (T - 1, 2N), geodesic (T, N)) int64 of the packed network ``bits``
         (T, N, W) uint32 (``pack_network``); a family that is switched off is None"""
-        bits = np.ascontiguousarray(bits, dtype=np.uint32)
-        if bits.shape != (self.T, self.N, packed_row_words(self.N)):
-            raise ValueError('bits has shape %s, expected %s'
-                             % (bits.shape, (self.T, self.N, packed_row_words(self.N))))
+        bits = self._packed(bits, 'bits')
         ov, st, geo = self._gof_dynamic_records((), temporal, geodesic)
         self._ck(self._L.dlsm_gof_dynamic_observed(
             self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(ov) if temporal else None,
@@ -841,29 +846,13 @@ class Chain(object):
     def ic_accumulate(self, bits, Xs, intercepts, radii=None, want_pointwise=False):
         """Pointwise log-likelihood of the packed network ``bits`` (T, N, W) uint32 (``pack_network``)
         over the S posterior samples ``Xs`` (S, T, N, D), ``intercepts`` (S,) or (S, 2), ``radii`` (S, N)
-        (directed and case-control chains), reduced on the device (csrc/kernels_ic.hpp).  Returns
-        ``totals`` (T, 5) - per time step sum lppd, sum var, sum mean, sum (lppd - var)^2, dyads - and
-        ``sample_loglik`` (S, T), the network log-likelihood of each sample; ``want_pointwise``: also
-        (T, N, N, 2), (lppd, var) per dyad (undirected: i < j filled, the rest 0)."""
-        bits = np.ascontiguousarray(bits, dtype=np.uint32)
-        if bits.shape != (self.T, self.N, packed_row_words(self.N)):
-            raise ValueError('bits has shape %s, expected %s'
-                             % (bits.shape, (self.T, self.N, packed_row_words(self.N))))
-        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
-        S = Xs.shape[0]
-        if S < 1:
-            raise ValueError('needs at least one sample')
-        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
-        b = np.asarray(intercepts, dtype=np.float64)
-        if b.ndim == 1 and self.model == UNDIRECTED:
-            b = np.stack([b, np.zeros_like(b)], axis=1)
-        b = _f64(b, (S, 2), 'intercepts')
-        if self.model == UNDIRECTED:
-            r = None
-        else:
-            if radii is None:
-                raise ValueError('directed models need radii')
-            r = _f64(radii, (S, self.N), 'radii')
+        (directed and case-control chains), reduced on the device (csrc/kernels_ic.hpp; the pass over the
+        samples: csrc/kernels_dyad_pass.hpp).  Returns ``totals`` (T, 5) - per time step sum lppd, sum var,
+        sum mean, sum (lppd - var)^2, dyads - and ``sample_loglik`` (S, T), the network log-likelihood of
+        each sample; ``want_pointwise``: also (T, N, N, 2), (lppd, var) per dyad (undirected: i < j filled,
+        the rest 0)."""
+        bits = self._packed(bits, 'bits')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii)
         totals = np.zeros((self.T, 5))
         sample_loglik = np.zeros((S, self.T))
         pw = np.zeros((self.T, self.N, self.N, 2)) if want_pointwise else None
@@ -880,29 +869,10 @@ class Chain(object):
         (undirected chains: either of (i, j), (j, i)).  Returns ``counts`` (T + 1, 4) uint64 - per time
         step and, in row T, pooled: n_pos, n_neg, u2, ties - and ``logloss_sum`` (T,);
         ``scores.scores_from_counts`` turns them into AUC, its bound and the mean log-loss."""
-        shape = (self.T, self.N, packed_row_words(self.N))
-        bits = np.ascontiguousarray(bits, dtype=np.uint32)
-        if bits.shape != shape:
-            raise ValueError('bits has shape %s, expected %s' % (bits.shape, shape))
+        bits = self._packed(bits, 'bits')
         if mask is not None:
-            mask = np.ascontiguousarray(mask, dtype=np.uint32)
-            if mask.shape != shape:
-                raise ValueError('mask has shape %s, expected %s' % (mask.shape, shape))
-        Xs = np.ascontiguousarray(Xs, dtype=np.float64)
-        S = Xs.shape[0]
-        if S < 1:
-            raise ValueError('needs at least one sample')
-        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
-        b = np.asarray(intercepts, dtype=np.float64)
-        if b.ndim == 1 and self.model == UNDIRECTED:
-            b = np.stack([b, np.zeros_like(b)], axis=1)
-        b = _f64(b, (S, 2), 'intercepts')
-        if self.model == UNDIRECTED:
-            r = None
-        else:
-            if radii is None:
-                raise ValueError('directed models need radii')
-            r = _f64(radii, (S, self.N), 'radii')
+            mask = self._packed(mask, 'mask')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii)
         counts = np.zeros((self.T + 1, 4), dtype=np.uint64)
         logloss_sum = np.zeros(self.T)
         self._ck(self._L.dlsm_score_accumulate(
@@ -936,17 +906,7 @@ class Chain(object):
         batch_len = int(batch_len)
         if not 1 <= batch_len <= seg_len // 2:
             raise ValueError('batch_len=%d is not between 1 and seg_len // 2 = %d' % (batch_len, seg_len // 2))
-        Xs = _f64(Xs, (S, self.T, self.N, self.D), 'Xs')
-        b = np.asarray(intercepts, dtype=np.float64)
-        if b.ndim == 1 and self.model == UNDIRECTED:
-            b = np.stack([b, np.zeros_like(b)], axis=1)
-        b = _f64(b, (S, 2), 'intercepts')
-        if self.model == UNDIRECTED:
-            r = None
-        else:
-            if radii is None:
-                raise ValueError('directed models need radii')
-            r = _f64(radii, (S, self.N), 'radii')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii)
         re_ = np.ascontiguousarray(np.ravel(rhat_edges), dtype=np.float64)
         ee = np.ascontiguousarray(np.ravel(ess_edges), dtype=np.float64)
         if re_.size > 16 or ee.size > 16:
@@ -977,24 +937,11 @@ class Chain(object):
         or on ``batch`` (samples per device batch, 0: automatic).  Returns ``(probas, paths, labels)``:
         (H, N, N) mean edge probabilities over the S samples, (S, H, N, D) positions if ``want_paths`` and
         (S, H, N) int32 labels if ``want_labels`` (mixture only), else None."""
-        X0 = np.ascontiguousarray(X0, dtype=np.float64)
-        S = X0.shape[0]
-        if S < 1:
-            raise ValueError('needs at least one sample')
-        X0 = _f64(X0, (S, self.N, self.D), 'X0')
+        X0, S = self._samples(X0, (self.N, self.D), 'X0')
         H = int(horizon)
         if H != horizon or H < 1:
             raise ValueError('horizon must be a positive integer, got %r' % (horizon,))
-        b = np.asarray(intercepts, dtype=np.float64)
-        if b.ndim == 1 and self.model == UNDIRECTED:
-            b = np.stack([b, np.zeros_like(b)], axis=1)
-        b = _f64(b, (S, 2), 'intercepts')
-        if self.model == UNDIRECTED:
-            r = None
-        else:
-            if radii is None:
-                raise ValueError('directed models need radii')
-            r = _f64(radii, (S, self.N), 'radii')
+        b, r = self._intercepts_radii(intercepts, radii, S)
         if z0 is None:
             if want_labels:
                 raise ValueError('the random walk has no labels')

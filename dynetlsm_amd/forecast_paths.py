@@ -26,8 +26,8 @@ counters, so every draw can be replayed on the host.
 """
 import numpy as np
 
+from ._trace import model_chain, point_estimate, sample_rows, trace_samples
 from .engine import Chain, pack_network
-from .ic import _sample_rows, _two_intercepts
 from .lsm import check_random_state
 from .scores import scores_from_counts
 
@@ -119,17 +119,15 @@ def _inputs(model, ids, estimate, n_samples):
             a = np.asarray(a)
             return np.ascontiguousarray(np.broadcast_to(a[None], (S,) + a.shape))
 
-        kw = dict(X0=tile(np.asarray(model.X_, dtype=np.float64)[-1]),
-                  intercepts=tile(_two_intercepts(np.asarray(model.intercept_, dtype=np.float64).reshape(1, -1))[0]),
-                  radii=tile(np.asarray(model.radii_, dtype=np.float64)) if directed else None)
+        X, ic, radii = point_estimate(model)
+        kw = dict(X0=tile(X[0, -1]), intercepts=tile(ic[0]), radii=tile(radii[0]) if directed else None)
         if kind != 'lsm':
             w = model.trans_weights_[-1] if kind == 'hdp' else model.trans_weight_
             kw.update(z0=tile(np.asarray(model.z_)[-1]), trans=tile(w), mu=tile(model.mu_), sigma=tile(model.sigma_),
                       lmbda=np.full(S, float(np.ravel(model.lambda_)[0])))
     else:
-        kw = dict(X0=np.ascontiguousarray(model.Xs_[ids, -1], dtype=np.float64),
-                  intercepts=_two_intercepts(np.asarray(model.intercepts_, dtype=np.float64)[ids]),
-                  radii=np.asarray(model.radiis_, dtype=np.float64)[ids] if directed else None)
+        X0, ic, radii = trace_samples(model, ids, step=-1)
+        kw = dict(X0=X0, intercepts=ic, radii=radii)
         if kind != 'lsm':
             w = model.weights_[ids, -1] if kind == 'hdp' else model.trans_weights_[ids]
             kw.update(z0=model.zs_[ids, -1], trans=w, mu=model.mus_[ids], sigma=model.sigmas_[ids],
@@ -173,7 +171,7 @@ def forecast(model, horizon=1, n_samples=None, estimate='posterior', random_stat
             raise ValueError('n_samples must be a positive integer, got %r' % (n_samples,))
         ids = None
     else:
-        ids = _sample_rows(model, n_samples)
+        ids = sample_rows(model, n_samples)
         S = len(ids)
     directed = bool(model.is_directed)
     rng = check_random_state(model.random_state if random_state is None else random_state)
@@ -182,16 +180,9 @@ def forecast(model, horizon=1, n_samples=None, estimate='posterior', random_stat
     mixture = 'z0' in kw
     _, N, D = kw['X0'].shape
 
-    chain = model.__dict__.get('chain_')
-    own = chain is None or getattr(chain, '_h', None) is None
-    if own:
-        chain = Chain(1, N, D, 'directed' if directed else 'undirected', device=getattr(model, 'device', 0))
-    try:
+    with model_chain(model, 1, N, D, directed) as chain:
         probas, paths, labels = chain.forecast_paths(horizon=H, seed=seed, want_paths=keep_paths,
                                                      want_labels=keep_paths and mixture, **kw)
-    finally:
-        if own:
-            chain.close()
     return ForecastResult(probas, ids, directed, paths, labels,
                           kw['intercepts'] if keep_paths else None, kw['radii'] if keep_paths else None,
                           device=getattr(model, 'device', 0))

@@ -16,7 +16,8 @@ are independent given the positions, so all persistence of ties comes from persi
 """
 import numpy as np
 
-from .engine import Chain, pack_network
+from ._trace import model_chain, observed_network, sample_rows, trace_samples
+from .engine import pack_network
 from .lsm import check_random_state
 
 __all__ = ['posterior_predictive_check', 'GofResult', 'derive_statistics', 'mc_p_values',
@@ -210,21 +211,6 @@ class GofResult(object):
         return self.summary()
 
 
-def _kept_start(model, n_rows):
-    from .hdp_lpcm import DynamicNetworkHDPLPCM
-    n_burn = model.n_burn_
-    if isinstance(model, DynamicNetworkHDPLPCM):      # its n_burn_ counts iterations: rows are thinned
-        n_burn = -(-n_burn // (model.thin or 1))
-    return min(int(n_burn), n_rows - 1)
-
-
-def _observed_network(model):
-    Y = np.asarray(model.Y_fit_) != 0         # a new boolean array
-    idx = np.arange(Y.shape[1])
-    Y[:, idx, idx] = False
-    return Y
-
-
 def _families(statistics):
     """'structural' | 'temporal' | 'geodesic' | 'all' | a tuple of the first three -> the tuple, in
     the order of FAMILIES"""
@@ -268,44 +254,24 @@ def posterior_predictive_check(model, n_samples=100, random_state=None, statisti
     if 'temporal' in families and np.shape(model.Y_fit_)[0] < 2:
         raise ValueError("statistics='temporal' needs at least two time steps, the model has T = %d"
                          % np.shape(model.Y_fit_)[0])
-    n_samples_i = int(n_samples)
-    if n_samples_i != n_samples or n_samples_i < 1:
-        raise ValueError('n_samples must be a positive integer, got %r' % (n_samples,))
-    n_rows = np.shape(model.intercepts_)[0]
-    start = _kept_start(model, n_rows)
-    if n_samples_i > n_rows - start:
-        raise ValueError('n_samples=%d exceeds the %d kept samples of the trace'
-                         % (n_samples_i, n_rows - start))
+    int(n_samples)            # (None is a TypeError: here the number of samples is required)
+    ids = sample_rows(model, n_samples)
     directed = bool(model.is_directed)
     rng = check_random_state(model.random_state if random_state is None else random_state)
     seed = int(rng.randint(0, 2 ** 31 - 1)) | (int(rng.randint(0, 2 ** 31 - 1)) << 31)
-
-    ids = np.round(np.linspace(start, n_rows - 1, n_samples_i)).astype(np.int64)
-    Xs = np.ascontiguousarray(model.Xs_[ids], dtype=np.float64)
-    S, T, N, D = Xs.shape
-    ic = np.asarray(model.intercepts_, dtype=np.float64)[ids].reshape(S, -1)
-    if ic.shape[1] == 1:
-        ic = np.concatenate([ic, np.zeros_like(ic)], axis=1)
-    radii = np.asarray(model.radiis_, dtype=np.float64)[ids] if directed else None
-
-    chain = model.__dict__.get('chain_')
-    own = chain is None or getattr(chain, '_h', None) is None
-    if own:
-        chain = Chain(T, N, D, 'directed' if directed else 'undirected', device=getattr(model, 'device', 0))
+    Xs, ic, radii = trace_samples(model, ids)
+    _, T, N, D = Xs.shape
     temporal, geodesic = 'temporal' in families, 'geodesic' in families
     observed, simulated = {}, {}
-    try:
-        bits = pack_network(_observed_network(model))
+    with model_chain(model, T, N, D, directed) as chain:
+        bits = pack_network(observed_network(model))
         if 'structural' in families:
             observed = derive_statistics(chain.gof_observed(bits), N, directed)
-            simulated = derive_statistics(chain.gof_simulate(Xs, ic[:, :2], radii, seed=seed), N, directed)
+            simulated = derive_statistics(chain.gof_simulate(Xs, ic, radii, seed=seed), N, directed)
         if temporal or geodesic:
             obs_rec = chain.gof_dynamic_observed(bits, temporal=temporal, geodesic=geodesic)
-            sim_rec = chain.gof_dynamic_simulate(Xs, ic[:, :2], radii, seed=seed, temporal=temporal,
+            sim_rec = chain.gof_dynamic_simulate(Xs, ic, radii, seed=seed, temporal=temporal,
                                                  geodesic=geodesic)
-    finally:
-        if own:
-            chain.close()
     if temporal or geodesic:
         observed.update(derive_dynamic_statistics(*obs_rec, None, N, directed))
         simulated.update(derive_dynamic_statistics(*sim_rec, None, N, directed))

@@ -7,8 +7,8 @@ observed dyads over the posterior samples of the trace,
 
 with eta the linear predictor of the model (``b - |x_i - x_j|`` undirected, the directed model of
 ``metrics.py`` (probas_) for directed and case-control fits).  The device reduces it over the samples
-in one pass without storing it (``Chain.ic_accumulate``: csrc/kernels_ic.hpp); the host turns the
-sums into the criteria:
+in one pass without storing it (``Chain.ic_accumulate``: csrc/kernels_ic.hpp, on the shared pass of
+csrc/kernels_dyad_pass.hpp); the host turns the sums into the criteria:
 
 * WAIC (Watanabe 2010; Vehtari, Gelman & Gabry 2017): ``lppd = sum log mean_s exp(l_s)``,
   ``p_waic = sum var_s(l_s)``, ``elpd_waic = lppd - p_waic``, ``waic = -2 elpd_waic`` and the standard
@@ -22,8 +22,8 @@ Lower ``waic`` / ``dic`` (higher ``elpd_waic``) is better.
 """
 import numpy as np
 
-from .engine import Chain, pack_network
-from .gof import _kept_start, _observed_network
+from ._trace import model_chain, observed_network, point_estimate, sample_rows, trace_samples
+from .engine import pack_network
 
 __all__ = ['information_criteria', 'compare_information_criteria', 'ICResult']
 
@@ -120,34 +120,6 @@ def _se(sum_elpd, sum_elpd_sq, n):
         return np.where(n > 1, np.sqrt(n * np.maximum(var, 0.0)), 0.0)
 
 
-def _two_intercepts(ic):
-    ic = np.asarray(ic, dtype=np.float64)
-    ic = ic.reshape(ic.shape[0], -1)
-    if ic.shape[1] == 1:
-        ic = np.concatenate([ic, np.zeros_like(ic)], axis=1)
-    return np.ascontiguousarray(ic[:, :2])
-
-
-def _sample_rows(model, n_samples):
-    """the trace rows a pass over the posterior uses: all kept rows (after the burn-in), or
-    ``n_samples`` of them evenly spaced as ``posterior_predictive_check`` picks them"""
-    if not hasattr(model, 'Y_fit_') or not hasattr(model, 'intercepts_'):
-        raise ValueError('Model not fit.')
-    n_rows = np.shape(model.intercepts_)[0]
-    start = _kept_start(model, n_rows)
-    if n_samples is None:
-        ids = np.arange(start, n_rows, dtype=np.int64)
-    else:
-        n_samples_i = int(n_samples)
-        if n_samples_i != n_samples or n_samples_i < 1:
-            raise ValueError('n_samples must be a positive integer, got %r' % (n_samples,))
-        if n_samples_i > n_rows - start:
-            raise ValueError('n_samples=%d exceeds the %d kept samples of the trace'
-                             % (n_samples_i, n_rows - start))
-        ids = np.round(np.linspace(start, n_rows - 1, n_samples_i)).astype(np.int64)
-    return ids
-
-
 def information_criteria(model, n_samples=None, pointwise=False):
     """WAIC and DIC of a fitted ``DynamicNetworkLSM`` (undirected, directed or case-control),
     ``DynamicNetworkHDPLPCM`` or ``DynamicNetworkLPCM``, for comparing fits of the same network
@@ -162,28 +134,15 @@ def information_criteria(model, n_samples=None, pointwise=False):
 
     Returns an ``ICResult``.
     """
-    ids = _sample_rows(model, n_samples)
+    ids = sample_rows(model, n_samples)
     directed = bool(model.is_directed)
-    Xs = np.ascontiguousarray(model.Xs_[ids], dtype=np.float64)
-    S, T, N, D = Xs.shape
-    ic = _two_intercepts(np.asarray(model.intercepts_, dtype=np.float64)[ids])
-    radii = np.asarray(model.radiis_, dtype=np.float64)[ids] if directed else None
-    # the point estimate of the fit, for DIC's d_hat
-    X_hat = np.ascontiguousarray(model.X_, dtype=np.float64)[None]
-    ic_hat = _two_intercepts(np.asarray(model.intercept_, dtype=np.float64).reshape(1, -1))
-    radii_hat = np.asarray(model.radii_, dtype=np.float64)[None] if directed else None
-    bits = pack_network(_observed_network(model))
-
-    chain = model.__dict__.get('chain_')
-    own = chain is None or getattr(chain, '_h', None) is None
-    if own:
-        chain = Chain(T, N, D, 'directed' if directed else 'undirected', device=getattr(model, 'device', 0))
-    try:
+    Xs, ic, radii = trace_samples(model, ids)
+    _, T, N, D = Xs.shape
+    X_hat, ic_hat, radii_hat = point_estimate(model)      # for DIC's d_hat
+    bits = pack_network(observed_network(model))
+    with model_chain(model, T, N, D, directed) as chain:
         out = chain.ic_accumulate(bits, Xs, ic, radii, want_pointwise=pointwise)
         _, loglik_hat = chain.ic_accumulate(bits, X_hat, ic_hat, radii_hat)
-    finally:
-        if own:
-            chain.close()
     return ICResult(ids, out[0], out[1], loglik_hat[0], directed, N, out[2] if pointwise else None)
 
 

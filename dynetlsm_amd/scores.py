@@ -8,7 +8,8 @@ The reference has ``auc_`` (metrics.py:10-24): the probabilities of the one sele
 
 over S posterior samples (eta: ``b - |x_i - x_j|`` undirected, the directed model of ``metrics.py``
 (probas_) for directed and case-control fits), counts a 24-bit rank key of pbar into histograms and
-returns exact integers (``Chain.score_accumulate``: csrc/kernels_score.hpp):
+returns exact integers (``Chain.score_accumulate``: csrc/kernels_score.hpp, on the shared pass of
+csrc/kernels_dyad_pass.hpp):
 
     n_pos, n_neg   scored dyads with y = 1 / y = 0
     u2             sum_b pos_b (2 cumneg_b + neg_b): twice the Mann-Whitney statistic of the keys
@@ -22,9 +23,8 @@ import math
 
 import numpy as np
 
-from .engine import Chain, pack_network
-from .gof import _observed_network
-from .ic import _sample_rows, _two_intercepts
+from ._trace import model_chain, observed_network, point_estimate, sample_rows, trace_samples
+from .engine import pack_network
 
 __all__ = ['in_sample_scores', 'scores_from_counts', 'ScoreResult']
 
@@ -140,30 +140,18 @@ def in_sample_scores(model, n_samples=None, estimate='posterior_mean'):
     """
     if estimate not in ('posterior_mean', 'map'):
         raise ValueError("estimate must be 'posterior_mean' or 'map', got %r" % (estimate,))
-    ids = _sample_rows(model, n_samples)
+    ids = sample_rows(model, n_samples)
     directed = bool(model.is_directed)
     if estimate == 'map':
         ids = None
-        Xs = np.ascontiguousarray(model.X_, dtype=np.float64)[None]
-        ic = _two_intercepts(np.asarray(model.intercept_, dtype=np.float64).reshape(1, -1))
-        radii = np.asarray(model.radii_, dtype=np.float64)[None] if directed else None
+        Xs, ic, radii = point_estimate(model)
     else:
-        Xs = np.ascontiguousarray(model.Xs_[ids], dtype=np.float64)
-        ic = _two_intercepts(np.asarray(model.intercepts_, dtype=np.float64)[ids])
-        radii = np.asarray(model.radiis_, dtype=np.float64)[ids] if directed else None
+        Xs, ic, radii = trace_samples(model, ids)
     _, T, N, D = Xs.shape
-    Y = _observed_network(model)
+    Y = observed_network(model)
     bits = pack_network(Y)
     excluded = _excluded_dyads(model, Y.shape, directed)
     mask = pack_network(excluded) if excluded is not None else None
-
-    chain = model.__dict__.get('chain_')
-    own = chain is None or getattr(chain, '_h', None) is None
-    if own:
-        chain = Chain(T, N, D, 'directed' if directed else 'undirected', device=getattr(model, 'device', 0))
-    try:
+    with model_chain(model, T, N, D, directed) as chain:
         counts, logloss_sum = chain.score_accumulate(bits, Xs, ic, radii, mask=mask)
-    finally:
-        if own:
-            chain.close()
     return scores_from_counts(counts, logloss_sum, ids, directed)
