@@ -15,6 +15,7 @@ from . import metrics  # noqa
 from . import model_selection  # noqa
 from .gof import posterior_predictive_check, GofResult  # noqa
 from .ic import information_criteria, compare_information_criteria, ICResult  # noqa
+from .loo import loo, compare_loo, LooResult  # noqa
 from .scores import in_sample_scores, ScoreResult  # noqa
 from .convergence import convergence_diagnostics, ConvergenceResult  # noqa
 from . import forecast  # noqa  (the one-step module; calling it is forecast_paths.forecast)
@@ -24,6 +25,6 @@ __version__ = '0.1.0'
 __all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
            'DynamicNetworkLSM', 'DynamicNetworkHDPLPCM', 'DynamicNetworkLPCM',
            'DirectedCaseControlSampler', 'posterior_predictive_check', 'GofResult',
-           'information_criteria', 'compare_information_criteria', 'ICResult',
+           'information_criteria', 'compare_information_criteria', 'ICResult', 'loo', 'compare_loo', 'LooResult',
            'in_sample_scores', 'ScoreResult', 'convergence_diagnostics', 'ConvergenceResult', 'forecast',
            'ForecastResult']

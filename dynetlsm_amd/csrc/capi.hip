@@ -36,6 +36,7 @@
 #include "kernels_ic.hpp"
 #include "kernels_score.hpp"
 #include "kernels_conv.hpp"
+#include "kernels_loo.hpp"
 #include "kernels_missing.hpp"
 #include "host_draws.hpp"
 
@@ -2214,6 +2215,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_ic.hpp"
 #include "capi_score.hpp"
 #include "capi_conv.hpp"
+#include "capi_loo.hpp"
 #include "capi_forecast_paths.hpp"
 #include "capi_hdp.hpp"
 

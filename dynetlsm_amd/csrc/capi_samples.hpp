@@ -60,9 +60,10 @@ struct ResidentSamples {
     const uint32_t *host_bits = nullptr, *host_mask = nullptr;      // what alloc was given: upload copies these
     DevBuf X, B, R, bits, mask, tiles;
 
-    explicit ResidentSamples(dlsm_chain *h)
+    // tile_rows: the tile height of the pass; 0: IcPlan's (capi_loo.hpp has a height of its own)
+    explicit ResidentSamples(dlsm_chain *h, int tile_rows = 0)
         : directed(h->model != DLSM_UNDIRECTED),
-          host_tiles(ic_tiles(h->N, h->D <= 4 ? IcPlan<1>::TI : IcPlan<8>::TI, directed)),
+          host_tiles(ic_tiles(h->N, tile_rows ? tile_rows : h->D <= 4 ? IcPlan<1>::TI : IcPlan<8>::TI, directed)),
           n_tiles((int)host_tiles.size()) {}
 
     // DLSM_E_LIMIT unless the samples, the networks net and net_mask (each unless NULL), the tiles and the caller's

@@ -924,6 +924,31 @@ class Chain(object):
         out = (hist_rhat, hist_ess, node_rhat, node_ess)
         return out + (pw,) if want_pointwise else out
 
+    # -- PSIS-LOO (no reference counterpart) -----------------------------------------------------
+    def loo_accumulate(self, bits, Xs, intercepts, radii=None, k_edges=(), want_pointwise=False):
+        """Pareto-smoothed importance-sampling leave-one-out of every dyad of the packed network ``bits``
+        over the S samples (arguments as ``ic_accumulate``), in one pass on the device
+        (csrc/kernels_loo.hpp; the fit: csrc/psis_tail.hpp; the definition: include/dynetlsm_hip.h).
+        Returns ``totals`` (T, 5) - per time step sum elpd_loo, sum elpd_loo^2, sum lppd, dyads, unfitted
+        dyads -, ``hist_k`` (T, len(k_edges) + 1) uint64 - the bin of a Pareto shape k is the number of
+        edges <= it, unfitted dyads (k = +inf) fall into the last one - and ``node_k_max`` (T, N), the
+        largest k over the dyads of each node; ``want_pointwise``: also (T, N, N, 2), (elpd_loo, k) per
+        dyad (undirected: i < j filled, the rest 0)."""
+        bits = self._packed(bits, 'bits')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii)
+        ke = np.ascontiguousarray(np.ravel(k_edges), dtype=np.float64)
+        if ke.size > 16:
+            raise ValueError('at most 16 edges per histogram')
+        totals = np.zeros((self.T, 5))
+        hist_k = np.zeros((self.T, ke.size + 1), dtype=np.uint64)
+        node_k = np.zeros((self.T, self.N))
+        pw = np.zeros((self.T, self.N, self.N, 2)) if want_pointwise else None
+        self._ck(self._L.dlsm_loo_accumulate(
+            self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(Xs), _p(b), _p(r) if r is not None else None,
+            int(S), _p(ke) if ke.size else None, int(ke.size), _p(totals),
+            hist_k.ctypes.data_as(_lib.c_u64_p), _p(node_k), _p(pw) if want_pointwise else None))
+        return (totals, hist_k, node_k, pw) if want_pointwise else (totals, hist_k, node_k)
+
     # -- multi-step posterior predictive forecasts (the reference: one step, undirected, on the host) ----
     def forecast_paths(self, X0, intercepts, radii=None, z0=None, trans=None, mu=None, sigma=None, lmbda=None,
                        sigma_sq=0.0, horizon=1, seed=0, first_index=0, batch=0, want_paths=False,

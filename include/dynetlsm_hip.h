@@ -489,6 +489,32 @@ int dlsm_convergence_accumulate(dlsm_chain *h, const double *Xs, const double *i
                                 uint64_t *hist_ess, double *node_rhat_max, double *node_ess_min,
                                 double *pointwise);
 
+/* ---- PSIS-LOO (Pareto-smoothed importance-sampling leave-one-out) -------- */
+/* No reference counterpart.  For every dyad of the packed network `bits` (as dlsm_ic_accumulate takes it: the
+ * same dyads, the same pointwise log-likelihood l_s, the same samples Xs S*T*N*D, intercepts S*2, radii S*N or
+ * NULL), in one pass over the samples, PSIS as the R package loo does it with r_eff = 1:
+ *   M = min(floor(S/5), ceil(3 sqrt(S))); lr_s = min_s l_s - l_s; the tail is the M largest lr, lr_cut the
+ *   next one below.  With M >= 5, a tail that is not constant (lr_(M) - lr_(1) >= DBL_EPSILON/100) and a finite
+ *   fit, the generalised Pareto fit of Zhang & Stephens 2009 to exp(lr) - exp(lr_cut) gives (k, sigma), k takes
+ *   the adjustment (M k + 5)/(M + 10), and the tail's lr are replaced in their order by
+ *   lw_(m) = min(0, log(exp(lr_cut) + sigma expm1(-k log1p(-p_m))/k)), p_m = (m - 0.5)/M.  Otherwise the dyad is
+ *   unfitted: k = +inf and lw = lr (csrc/psis_tail.hpp).
+ *   elpd_loo = logsumexp_s(lw_s + l_s) - logsumexp_s(lw_s),  lppd = logsumexp_s(l_s) - log S
+ * Outputs (bin of a value: the number of edges <= it, so +inf falls into the last one):
+ *   totals      T*5: per time step sum elpd_loo, sum elpd_loo^2, sum lppd, number of dyads, unfitted dyads
+ *   hist_k      T*(n_edges+1) uint64: dyads of time step t per bin of k over k_edges
+ *   node_k_max  T*N: the largest k over the dyads that contain the node (directed: as sender or receiver);
+ *               -inf for a node without a dyad (N = 1)
+ *   pointwise   NULL or T*N*N*2: (elpd_loo, k) of dyad (t, i, j); undirected: i < j filled, the rest 0
+ * Every sum is taken in a fixed order and only integer atomics are used: the same call returns the same bits.
+ * More than 16 edges -> DLSM_E_ARG; edges that are not finite and ascending, a set diagonal or padding bit, a
+ * radius <= 0 -> DLSM_E_DATA.  All S samples are held on the device at once, and every dyad keeps its M + 1
+ * smallest l_s in the LDS; if either does not fit -> DLSM_E_LIMIT, and the message names the largest S that
+ * does. */
+int dlsm_loo_accumulate(dlsm_chain *h, const uint32_t *bits, const double *Xs, const double *intercepts,
+                        const double *radii, int S, const double *k_edges, int n_edges, double *totals,
+                        uint64_t *hist_k, double *node_k_max, double *pointwise);
+
 /* ---- multi-step posterior predictive forecasts --------------------------- */
 /* The reference has only the one-step undirected form (hdp_lpcm.py:555-626, drawn on the host).  One
  * trajectory of H future time steps per sample s, started at the sample's last time step X0 S*N*D:
