@@ -1182,12 +1182,12 @@ static int resolve_sweep_algo(const dlsm_chain *h, int algo) {
 }
 
 // algo 4: one fused launch per batch, resolve(b) beside eval(b + 1) (kernels_spec_pipe.hpp)
-template <int DD, int MODEL, int G = 1>
+template <int DD, int MODEL>
 static void launch_pipe_step(dlsm_chain *h, hipStream_t q, const ChainView &v, const PipeBuf &pb, dim3 grid,
                              size_t lds, int l) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->profiling) { hipEventCreate(&e0); hipEventCreate(&e1); }
-    hipExtLaunchKernelGGL((k_pipe_step<DD, MODEL, G>), grid, dim3(PP_THREADS), lds, q,
+    hipExtLaunchKernelGGL((k_pipe_step<DD, MODEL>), grid, dim3(PP_THREADS), lds, q,
                           e0, e1, 0, v, pb, l);
     if (h->profiling) h->prof[DLSM_K_SWEEP_EVAL].pending.emplace_back(e0, e1);
 }
@@ -1221,11 +1221,10 @@ static int check_pipe_err(dlsm_chain *h) {
     return DLSM_OK;
 }
 
-// one batch resolved (and one evaluated) per launch (the kernels' template parameter G = 1: the two-batch
-// form, algo 6, and the single persistent launch, algo 7, measured slower and were removed in round 5)
+// one batch resolved (and one evaluated) per launch (the two-batch form, algo 6, and the single persistent
+// launch, algo 7, measured slower and were removed in round 5)
 template <int DD>
 static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
-    constexpr int G = 1;
     hipStream_t q = sc.stream;
     const Knobs &kn = sc.knobs;
     const int N = h->N, T = h->T;
@@ -1243,13 +1242,12 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
     }
     auto even2 = [](size_t n) { return (n + 1) / 2 * 2; };
     const size_t n_prop = even2((size_t)T * N * (2 * DD + 2));
-    const int xr = (2 * G - 1) * PP_B;
-    const size_t n_full0 = (size_t)2 * G * T * PP_B * parts * 2;
-    const size_t n_h = (size_t)2 * G * T * PP_B * PP_B;
-    const size_t n_hx = (size_t)2 * G * T * xr * PP_B;
-    const size_t n_acc = even2(((size_t)T * 2 * G * PP_ACC + 1) / 2);   // int32 pairs
+    // (PipeBuf: two batch slots of everything produced per batch)
+    const size_t n_full0 = (size_t)2 * T * PP_B * parts * 2;
+    const size_t n_h = pipe_h_doubles(T);
+    const size_t n_acc = even2(((size_t)T * 2 * PP_ACC + 1) / 2);   // int32 pairs
     const size_t n_xp = (size_t)T * PP_B;
-    const size_t need = (n_prop + n_full0 + n_h + n_hx + n_acc + 2 + n_xp) * sizeof(double);
+    const size_t need = (n_prop + n_full0 + n_h + n_acc + 2 + n_xp) * sizeof(double);
     if (h->pipe_cap < need) {
         if (h->pipe) hipFree(h->pipe);
         h->pipe = nullptr; h->pipe_cap = 0;
@@ -1257,14 +1255,12 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
         h->pipe_cap = need;
     }
     PipeBuf pb{};
-    pb.prop = h->pipe; pb.full0 = pb.prop + n_prop; pb.Hd = pb.full0 + n_full0;
-    pb.Hx = pb.Hd + n_h; pb.acc = (int32_t *)(pb.Hx + n_hx);
-    pb.consts = pb.Hx + n_hx + n_acc;
+    pb.prop = h->pipe; pb.full0 = pb.prop + n_prop; pb.H = pb.full0 + n_full0;
+    pb.acc = (int32_t *)(pb.H + n_h);
+    pb.consts = pb.H + n_h + n_acc;
     pb.xprod = pb.consts + 2;
-    pb.sync = nullptr; pb.nsync = 0; pb.queue0 = ne_wg;
     pb.lsm_draw = sc.draw_intercept ? h->lsm : nullptr;
     pb.parts = parts; pb.nbat = nbat;
-    pb.G = G; pb.xr = xr;
     pb.per = ((N + parts - 1) / parts + 63) / 64 * 64;      // parts start on a 64-neighbour boundary
     pb.nctrl = h->nctrl;
     // the resolvers' diagonal block by rows of PR_LD (an odd stride: row_resolve), the evaluators' exp table
@@ -1287,7 +1283,7 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
     ChainView v = h->view();
     {   // the evaluators' arguments (kernels_pipe_lds.hpp) in one piece
         PipeLds &a = pb.lds;
-        a.X = v.X; a.ybits = v.ybits; a.prop = pb.prop; a.full0 = pb.full0; a.Hd = pb.Hd; a.acc = pb.acc;
+        a.X = v.X; a.ybits = v.ybits; a.prop = pb.prop; a.full0 = pb.full0; a.H = pb.H; a.acc = pb.acc;
         a.consts = pb.consts; a.xprod = pb.xprod;
         a.T = T; a.N = N; a.W = v.W; a.squared = v.squared; a.parts = parts; a.nbat = nbat;
         a.lds_cap = pipe_lds_trip_cap((N + 63) / 64, parts); a.xserve = 0;
@@ -1311,24 +1307,23 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     if (sc.alloc_only) return DLSM_OK;
     {   // the proposal pass, unless the previous iteration's last launch carried it
-        const ProposeBuf nb{pb.prop, pb.consts, pb.sync, pb.nsync, pb.queue0, pb.lsm_draw};
+        const ProposeBuf nb{pb.prop, pb.consts, pb.lsm_draw};
         if (!h->carry.drawn(iter.ptr ? -1L : (long)iter.value, nb))
             hipLaunchKernelGGL((k_pipe_propose<DD>), dim3((N + 255) / 256, T), dim3(256), 0, q, v, pb, iter);
         h->carry.taken(nb); sc.left_proposals = true;
     }
-    // launch l: even slices resolve batches G l .. / evaluate G (l + 1) .., odd slices one launch
+    // launch l: even slices resolve batch l / evaluate batch l + 1, odd slices one launch
     // behind; with a single slice (T == 1) the trailing odd-only launch is empty
-    const int nlaunch = (nbat + G - 1) / G;
-    const int last = T > 1 ? nlaunch : nlaunch - 1;
+    const int last = T > 1 ? nbat : nbat - 1;
     for (int l = -1; l <= last; ++l) {
         // (the head - the proposal pass above and launch -1 - may have been enqueued on the chain's second
         // queue already, beside the previous iteration's conjugate draws: capi_hdp.hpp)
         if (l == -1 && !iter.ptr && h->carry.head_done_for == (long)iter.value) continue;
         if (sc.head_only && l >= 0) break;
-        const bool any_eval = (G * (l + 1) < nbat) || (T > 1 && l >= 0 && G * l < nbat);
+        const bool any_eval = (l + 1 < nbat) || (T > 1 && l >= 0 && l < nbat);
         const int grid = T + (any_eval ? ne_wg : 0);
         const bool lng = !pb.lds_eval;       // (undirected model without the LDS evaluators: pipe_eval_item's pipelined trips)
-        if (l == last && !any_eval && sc.want_post_ride && G == 1 && h->model == DLSM_UNDIRECTED &&
+        if (l == last && !any_eval && sc.want_post_ride && h->model == DLSM_UNDIRECTED &&
             !h->profiling && l >= 0 && T + 4 <= PS_BLOCKS) {
             // the centring sums ride in the resolve-only launch (kernels_spec_pipe.hpp): nwg rider
             // records + one per slice from the resolvers
@@ -1351,12 +1346,11 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
             a.nbE = (beE >= 0 && beE < nbat) ? std::min(PP_B, N - beE * PP_B) : 0;
             a.nbO = (beO >= 0 && beO < nbat) ? std::min(PP_B, N - beO * PP_B) : 0;
             a.nslE = a.nbE > 0 ? nE : 0; a.nslO = a.nbO > 0 ? nO : 0;
-            const int gx = PP_B / PP_WAVES, nsl = a.nslE + a.nslO;
+            const int nsl = a.nslE + a.nslO;
             a.nsl_magic = (65536u + (uint32_t)nsl - 1u) / (uint32_t)nsl;
             // serving wavefronts per evaluator workgroup (pipe_xserve_request): every launched one can serve
             a.xstride = (T * PP_B + ne_wg - 1) / ne_wg;
             pb.xserve = a.xserve = xserve_sweep && a.xstride <= PP_WAVES;
-            (void)gx;
             launch_pipe_step<DD, DLSM_UNDIRECTED>(h, q, v, pb, dim3(grid), lds, l);
         } else if (h->model == DLSM_UNDIRECTED)
             launch_pipe_step<DD, DLSM_UNDIRECTED>(h, q, v, pb, dim3(grid), lds, l);
@@ -1427,7 +1421,7 @@ static int launch_sweep_ccpipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
     pp.prop = pb.prop; pp.consts = consts;
     ChainView v = h->view();
     {   // the proposal pass, unless the previous iteration's last launch carried it
-        const ProposeBuf nb{pp.prop, pp.consts, nullptr, 0, 0, nullptr};
+        const ProposeBuf nb{pp.prop, pp.consts, nullptr};
         if (!h->carry.drawn(iter.ptr ? -1L : (long)iter.value, nb))
             hipLaunchKernelGGL((k_pipe_propose<DD>), dim3((N + 255) / 256, T), dim3(256), 0, q, v, pp, iter);
         h->carry.taken(nb); sc.left_proposals = true;

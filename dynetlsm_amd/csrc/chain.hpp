@@ -44,7 +44,6 @@ struct ChainView {
 struct LsmDeviceState;
 struct ProposeBuf {
     double *prop, *consts;
-    int32_t *sync; int nsync, queue0;
     LsmDeviceState *lsm_draw;   // not NULL: the pass also draws the undirected loop's intercept proposal
 };
 
@@ -99,7 +98,7 @@ struct SweepCarry {
     // were iteration `it`'s proposals (it < 0: counted on the device - never) drawn into these buffers
     bool drawn(long it, const ProposeBuf &nb) const {
         return it >= 0 && prop_drawn_for == it && next_prop_ok && next_prop.prop == nb.prop &&
-               next_prop.sync == nb.sync && next_prop.queue0 == nb.queue0 && next_prop.lsm_draw == nb.lsm_draw;
+               next_prop.consts == nb.consts && next_prop.lsm_draw == nb.lsm_draw;
     }
     // a pipelined sweep has taken the buffers `nb` (and whatever was drawn ahead into them)
     void taken(const ProposeBuf &nb) { next_prop = nb; next_prop_ok = true; prop_drawn_for = -1; }

@@ -102,38 +102,37 @@ __device__ __forceinline__ void pipe_cc_writeout(const ChainView &c, const PipeB
     if (m >= ncross + k) return;
     const double v = col[m];
     const double f = v == 0.0 ? 1.0 : exp(v);
-    if (m < ncross) pb.Hx[(((size_t)bb * c.T + t) * PP_B + m) * PP_B + k] = f;    // G = 1
-    else pb.Hd[(((size_t)bb * c.T + t) * PP_B + (m - ncross)) * PP_B + k] = f;
+    double *Hd = pb.H + ((size_t)bb * c.T + t) * PP_B * PP_B;           // the [m][k] blocks (PipeBuf)
+    double *Hx = Hd + pipe_h_cc_cross(c.T);
+    if (m < ncross) Hx[m * PP_B + k] = f;
+    else Hd[(m - ncross) * PP_B + k] = f;
 }
 
-// Resolve batch b of slice t: the fixed-point solve of k_spec_resolve for one batch, the
-// acceptances of its window's earlier batches (pipe_window_start) entering through gathered rows
-// of the cross block.  With G > 1 a workgroup resolves G batches one after the other; the list
-// of the batch it has just resolved is in sOwn (own_prev), the others come from memory.
-template <int D, int G>
-__device__ __forceinline__ void pipe_resolve(const ChainView &c, const PipeBuf &pb, int b, int t,
-                                             double *sH, double *sPart,
-                                             unsigned long long (*sMask)[2], int *sPrev,
-                                             unsigned char *sSat, int *sOwn, bool own_prev,
-                                             Stamps<PIPE_RES_T> rst) {
+// The dense case-control resolver (reached from k_pipe_step<D, DLSM_DIRECTED_CASE_CONTROL, 1> only; the exact
+// models' is row_resolve).  Resolve batch b of slice t: the fixed-point solve of k_spec_resolve for one batch, the
+// acceptances of the previous batch - the list the launch before left in memory - entering through gathered
+// rows of the cross block.
+template <int D>
+__device__ __forceinline__ void pipe_resolve_ccdense(const ChainView &c, const PipeBuf &pb, int b, int t,
+                                                     double *sH, double *sPart,
+                                                     unsigned long long (*sMask)[2], int *sPrev,
+                                                     unsigned char *sSat, Stamps<PIPE_RES_T> rst) {
     constexpr int PW = 2 * D + 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     DLSM_STAMP(rst, 0, (double)tid)
     const int N = c.N;
     const int j0 = b * PP_B;
     const int nb = min(PP_B, N - j0);
-    constexpr int G2 = 2 * G;
-    const int bb = b & (G2 - 1);
+    const int bb = b & 1;
     const int half = wave & 1, part = wave >> 1;
     const int k = 64 * half + lane;
     const bool owner = wave < 2;
     const bool valid = k < nb;
-    const double *Hd = pb.Hd + ((size_t)bb * c.T + t) * PP_B * PP_B;
-    const double *Hx = pb.Hx + ((size_t)bb * c.T + t) * ((G2 - 1) * PP_B) * PP_B;
-    int32_t *acct = pb.acc + (size_t)t * G2 * PP_ACC;
+    const double *Hd = pb.H + ((size_t)bb * c.T + t) * PP_B * PP_B;    // the [m][k] blocks (PipeBuf)
+    const double *Hx = Hd + pipe_h_cc_cross(c.T);
+    int32_t *acct = pb.acc + (size_t)t * 2 * PP_ACC;
     int32_t *accg = acct + (size_t)bb * PP_ACC;                // this batch's list
-    const int ws = pipe_window_start(b, G);
-    const int nwin = b - ws;                                    // earlier batches of the window: <= 3
+    const int32_t *lst = acct + (size_t)(bb ^ 1) * PP_ACC;     // the previous batch's
     // diagonal block -> LDS (unconditional clamped loads, see k_spec_resolve)
     double2 blk[8];
 #pragma unroll
@@ -141,23 +140,10 @@ __device__ __forceinline__ void pipe_resolve(const ChainView &c, const PipeBuf &
         const int q = min(u * PP_THREADS + tid, nb * (PP_B / 2) - 1);
         blk[u] = coh_load2<false>(Hd, (uint32_t)(((q >> 6) * PP_B + 2 * (q & 63)) * sizeof(double)));
     }
-    // their accepted nodes as rows of the cross block: row = 128 (batch - ws) + node
-    int cntw[3] = {0, 0, 0};
-#pragma unroll
-    for (int w = 0; w < G2 - 1; ++w)
-        if (w < nwin) {
-            const bool own = own_prev && ws + w == b - 1;
-            cntw[w] = own ? sOwn[0] : acct[(size_t)((ws + w) & (G2 - 1)) * PP_ACC];
-        }
-    const int nprev = cntw[0] + cntw[1] + cntw[2];
-#pragma unroll
-    for (int w = 0; w < G2 - 1; ++w)
-        if (w < nwin) {
-            const bool own = own_prev && ws + w == b - 1;
-            const int32_t *lst = own ? sOwn : acct + (size_t)((ws + w) & (G2 - 1)) * PP_ACC;
-            const int off = w == 0 ? 0 : (w == 1 ? cntw[0] : cntw[0] + cntw[1]);
-            for (int a = tid; a < cntw[w]; a += PP_THREADS) sPrev[off + a] = w * PP_B + lst[1 + a];
-        }
+    // the previous batch's accepted nodes: rows of the cross block
+    const int nprev = b > 0 ? lst[0] : 0;
+    static_assert(PP_B <= PP_THREADS, "one thread per entry of the previous batch's list");
+    if (tid < nprev) sPrev[tid] = lst[1 + tid];                 // (nprev <= PP_B)
     // multiplicative domain: r = exp(log-ratio of node k), lu = its uniform draw.  A node whose
     // log-ratio is beyond +-700 (exp would saturate) is resolved in the log domain instead -
     // log u against lr + the LOGS of its H factors - so that the decision is the sequential
@@ -210,17 +196,14 @@ __device__ __forceinline__ void pipe_resolve(const ChainView &c, const PipeBuf &
         double prod = 1.0;
         int a = part;
         if (!anysat) {
-            // PP_B / 8 = 16 rows per thread and trip (one trip per 128 accepted nodes): all their
-            // loads in flight together (clamped addresses, the factor of a row that is not there
-            // replaced by 1)
-            for (int base = 0; base < nprev; base += PP_B) {
-                double hh[PP_B / 8];
+            // PP_B / 8 = 16 rows per thread: all their loads in flight together (clamped addresses, the
+            // factor of a row that is not there replaced by 1)
+            double hh[PP_B / 8];
 #pragma unroll
-                for (int u = 0; u < PP_B / 8; ++u)
-                    hh[u] = coh_load<false>(colp + (size_t)sPrev[min(base + a + 8 * u, nprev - 1)] * PP_B);
+            for (int u = 0; u < PP_B / 8; ++u)
+                hh[u] = coh_load<false>(colp + (size_t)sPrev[min(a + 8 * u, nprev - 1)] * PP_B);
 #pragma unroll
-                for (int u = 0; u < PP_B / 8; ++u) prod *= base + a + 8 * u < nprev ? hh[u] : 1.0;
-            }
+            for (int u = 0; u < PP_B / 8; ++u) prod *= a + 8 * u < nprev ? hh[u] : 1.0;
         } else {
             double lsum = 0.0;
             for (; a < nprev; a += 8) {
@@ -306,19 +289,12 @@ __device__ __forceinline__ void pipe_resolve(const ChainView &c, const PipeBuf &
             metropolis_bookkeeping(st, na, ns, un, c.tune, c.tune_interval, accepted);
             c.step[tj] = st; c.nacc[tj] = na; c.nsteps[tj] = ns; c.until[tj] = un;
         }
-        // accepted nodes of this batch (ascending) for the cross terms of the batches that have it
-        // in their window: in memory for the launches to come, in LDS for this workgroup's next batch
+        // accepted nodes of this batch (ascending) for the cross terms of the next batch, whose window it is
         if (accepted) {
             const int base = half == 0 ? 0 : __popcll(m0);
-            const int at = 1 + base + __popcll(mine & ((1ull << lane) - 1ull));
-            accg[at] = k;
-            sOwn[at] = k;
+            accg[1 + base + __popcll(mine & ((1ull << lane) - 1ull))] = k;
         }
-        if (tid == 0) {
-            const int cnt = __popcll(m0) + __popcll(m1);
-            accg[0] = cnt;
-            sOwn[0] = cnt;
-        }
+        if (tid == 0) accg[0] = __popcll(m0) + __popcll(m1);
     }
     DLSM_STAMP(rst, 4, (double)cur)
     if (tid == 0) rst.flush();

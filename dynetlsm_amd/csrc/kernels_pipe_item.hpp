@@ -27,8 +27,8 @@ __device__ __forceinline__ void pipe_directed_term(RatioAcc &ra, double &exact, 
     ra.P1 *= fma(E, fast_exp(x1a), 1.0) * fma(E, fast_exp(x1g), 1.0);
 }
 
-// The H entries of a (slice, batch) - node kk has ncross + kk of them: the window's earlier batches
-// (cross block), then the earlier nodes of its own batch - as ONE flat list dealt out over the lanes
+// The H entries of a (slice, batch) - node kk has ncross + kk of them: the nodes of its window, the
+// previous batch (cross block), then the earlier nodes of its own batch - as ONE flat list dealt out over the lanes
 // working on the (slice, batch).  Rows are listed in PAIRS (r, nb - 1 - r), r < ceil(nb / 2): a pair
 // holds L = 2 ncross + nb - 1 entries whatever r, so f -> (pair, offset) is one quotient by a launch
 // constant and the pair's two rows are told apart by a compare - 15 vector instructions where the
@@ -89,21 +89,16 @@ __device__ __forceinline__ void pipe_h_operands(const ChainView &c, const double
 }
 // One H entry: flat index f of (slice t, batch be), operands o.  Rows of the H blocks are addressed as
 // 32-bit offsets from a scalar base.
-template <int D, int MODEL, int G, bool SQ>
+template <int D, int MODEL, bool SQ>
 __device__ __forceinline__ void pipe_h_entry(const ChainView &c, const PipeBuf &pb, int be, int nb, int t,
                                              const double *etab, int kk, int e, const PipeHPre<D> &o,
                                              Stamps<PIPE_ITEM_T> &st) {
     const int j0 = be * PP_B;
-    const int jprev = pipe_window_start(be, G) * PP_B;
+    const int jprev = pipe_window_start(be) * PP_B;
     const int ncross = j0 - jprev;
-    const int bb = be & (2 * G - 1);
+    const int bb = be & 1;
     const double E = pb.consts[0];
-    // one batch per launch: the blocks by ROWS of the later node (row_resolve); the [m][k] blocks of pipe_resolve
-    // are the dense case-control form's
-    constexpr bool HROWS = G == 1;
-    char *hbase = (char *)(pb.Hd + ((size_t)bb * c.T + t) * PP_B * (HROWS ? 2 * PP_B : PP_B));
-    const uint32_t hx_off = (uint32_t)((const char *)(pb.Hx + ((size_t)bb * c.T + t) * ((2 * G - 1) * PP_B) * PP_B) -
-                                       (const char *)hbase);                          // one allocation
+    char *hbase = (char *)(pb.H + ((size_t)bb * c.T + t) * PP_H_SLICE);       // the factors by rows (PipeBuf)
     const int jm_ = jprev + e;                 // jprev + ncross == j0
     double xm0[D], xm1[D], xa0[D], xa1[D];
 #pragma unroll
@@ -150,16 +145,14 @@ __device__ __forceinline__ void pipe_h_entry(const ChainView &c, const PipeBuf &
         // exp(delta(b) - delta(a)) without the logs: the products divide out
         h = ((rb.P0 * rq.P1) / (rb.P1 * rq.P0)) * exp((rb.lin - rq.lin) + (eb - eq));
     }
-    if (HROWS)      // one row of 2 PP_B factors per later node kk - its window's nodes, then its own
-                    // batch's - so that a wavefront's entries are contiguous
-        coh_store<false>((double *)(hbase + (uint32_t)(kk * (2 * PP_B) + (cross ? e : PP_B + m)) * 8u), h);
-    else
-        coh_store<false>((double *)(hbase + ((cross ? hx_off : 0u) + (uint32_t)(m * PP_B + kk) * 8u)), h);
+    // one row of PP_H_ROW factors per later node kk - its window's nodes, then its own batch's - so that a
+    // wavefront's entries are contiguous
+    coh_store<false>((double *)(hbase + (uint32_t)(kk * PP_H_ROW + (cross ? e : PP_B + m)) * 8u), h);
 }
 
 // The item's tail: wavefront reductions, the (sum, ratio) record, and this lane's share of the
 // batch's H entries.
-template <int D, int MODEL, int G>
+template <int D, int MODEL>
 __device__ __forceinline__ void pipe_item_finish(const ChainView &c, const PipeBuf &pb, int be, int nb,
                                                  int t, int k, int p, int lane, const double *etab,
                                                  double acc, RatioAcc &ra, bool noflush,
@@ -167,9 +160,9 @@ __device__ __forceinline__ void pipe_item_finish(const ChainView &c, const PipeB
     constexpr int PW = 2 * D + 2;
     const int N = c.N, W = c.W;
     const int j0 = be * PP_B;
-    const int jprev = pipe_window_start(be, G) * PP_B;
+    const int jprev = pipe_window_start(be) * PP_B;
     const int ncross = j0 - jprev;
-    const int bb = be & (2 * G - 1);
+    const int bb = be & 1;
     const double *props = pb.prop + (size_t)t * N * PW;
     const int hround = nb * pb.parts * 64;
     const PipeHList hl = pipe_h_list(ncross, nb);
@@ -193,14 +186,15 @@ __device__ __forceinline__ void pipe_item_finish(const ChainView &c, const PipeB
     const char *ytrows = MODEL == DLSM_DIRECTED ? (const char *)(c.ytbits + (size_t)t * N * W) : nullptr;
     int f = hf0;
 #define DLSM_H_CALL(SQ_, KK_, E_, O_, STAMP_)                                                         \
-    (st.arm(STAMP_), pipe_h_entry<D, MODEL, G, SQ_>(c, pb, be, nb, t, etab, KK_, E_, O_, st))
-    // HSHIFT (the launch-per-batch evaluators: a workgroup's 16 wavefronts hold items k0 .. k0 + 15 of one
-    // part, wavefronts w, w + 4, w + 8, w + 12 share a SIMD): the LAST wavefront of a SIMD hands its
-    // first-round entries to the FIRST one - the same arithmetic on the same SIMD, but no longer the launch's tail
-    constexpr bool HSHIFT = DLSM_H_SHIFT != 0;
+    (st.arm(STAMP_), pipe_h_entry<D, MODEL, SQ_>(c, pb, be, nb, t, etab, KK_, E_, O_, st))
+    // A workgroup's 16 wavefronts hold items k0 .. k0 + 15 of one part, wavefronts w, w + 4, w + 8, w + 12 share a
+    // SIMD: the LAST wavefront of a SIMD hands its first-round entries to the FIRST one - the same arithmetic on the
+    // same SIMD, but no longer the launch's tail.  (Under oldest-first issue this measured slower, 10.77 against
+    // 10.54 us; with the items advancing together - DLSM_TRIP_PRIO_STEP - the first wavefront of a SIMD still leaves
+    // ~1.8 us before the last one, whose entry is the launch's tail: 9.82 -> 9.58 us per launch, C2 4565 -> 4660 it/s)
     const int wig = (int)(threadIdx.x >> 6);
     bool first = true;
-    if (HSHIFT && wig >= 12 && f < hround) f += hround;           // handed over (its later rounds stay)
+    if (wig >= 12 && f < hround) f += hround;           // handed over (its later rounds stay)
     for (; f < hl.nslots; f += hround) {
         int kk, e;
         if (pipe_h_decode(f, hl, ncross, nb, kk, e)) {
@@ -209,7 +203,7 @@ __device__ __forceinline__ void pipe_item_finish(const ChainView &c, const PipeB
             if (c.squared) DLSM_H_CALL(true, kk, e, o, f == hf0);
             else DLSM_H_CALL(false, kk, e, o, f == hf0);
         }
-        if (HSHIFT && first && wig < 4 && k + 12 < nb) {
+        if (first && wig < 4 && k + 12 < nb) {
             // ... and the first-round entries of item k + 12 (same part, same slice: the SIMD's last wavefront)
             const int f2 = hf0 + 12 * pb.parts * 64;
             if (f2 < hl.nslots && pipe_h_decode(f2, hl, ncross, nb, kk, e)) {
@@ -237,9 +231,7 @@ __device__ __forceinline__ void pipe_item_prologue(const ChainView &c, const Pip
                                                    int k, int p, int lane, PipeItemPre<D> &q) {
     constexpr int PW = 2 * D + 2;
     const int N = c.N, W = c.W;
-#if DLSM_TRIP_PRIO
     __builtin_amdgcn_s_setprio(3);          // from the item's first instruction: its loads leave at once
-#endif
     const int jk = be * PP_B + k;
     const double *props = pb.prop + (size_t)t * N * PW;
     const uint32_t *yr = c.ybits + ((size_t)t * N + jk) * W;
@@ -274,7 +266,7 @@ __host__ __device__ constexpr int pipe_prefetch_trips(int D) {
 // prefetched ones are software-pipelined.  (Round 6 removed the forms measured and dropped in rounds 3 - 5: rows
 // staged in LDS by a persistent launch, the lane's H entry at the head of the item or requested mid-way, and
 // their measurement switches - profiles/r04_h_entry_ablation.md holds their numbers.)
-template <int D, int MODEL, bool TP, int G>
+template <int D, int MODEL, bool TP>
 __device__ __forceinline__ void pipe_eval_item(const ChainView &c, const PipeBuf &pb, int be,
                                                int nb, int t, int k, int p, int lane,
                                                const double *etab, const PipeItemPre<D> &pre,
@@ -283,9 +275,7 @@ __device__ __forceinline__ void pipe_eval_item(const ChainView &c, const PipeBuf
     const int N = c.N, W = c.W;
     DLSM_STAMP(st, 0, (double)lane)
     const int j0 = be * PP_B, jk = j0 + k;
-    const int jprev = pipe_window_start(be, G) * PP_B;      // nodes >= jprev: snapshot positions
-    const int ncross = j0 - jprev;
-    const int bb = be & (2 * G - 1);
+    const int jprev = pipe_window_start(be) * PP_B;         // nodes >= jprev: snapshot positions
     const double *Xt = c.X + (size_t)t * N * D;
     const double *props = pb.prop + (size_t)t * N * PW;
     const uint32_t *yr = c.ybits + ((size_t)t * N + jk) * W;
@@ -425,7 +415,7 @@ __device__ __forceinline__ void pipe_eval_item(const ChainView &c, const PipeBuf
 #undef DLSM_PIPE_REQUEST
 #undef DLSM_PIPE_MASKS
 #undef DLSM_PIPE_TERM
-    pipe_item_finish<D, MODEL, G>(c, pb, be, nb, t, k, p, lane, etab, acc, ra, noflush, st);
+    pipe_item_finish<D, MODEL>(c, pb, be, nb, t, k, p, lane, etab, acc, ra, noflush, st);
     if (lane == 0) st.flush();
 }
 

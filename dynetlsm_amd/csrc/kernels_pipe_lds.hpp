@@ -138,11 +138,7 @@ __device__ __forceinline__ void pipe_lds_trips(int nw64, int P, const PipePlan &
                     const double *rowm = sM + ((size_t)u * 64 + lane) * D;
 #pragma unroll
                     for (int d = 0; d < D; ++d) xm1[d] = rowm[d];
-#ifdef DLSM_X_LDS_H1
-                    const double h = fma(0.0, xm1[0], 1.0);
-#else
                     const double h = pipe_h_finish<D, SQ>(xm1, xk0, xk1, d0, d1, e0, e1, f0, f1, yb, E, etab);
-#endif
                     hrow[(wq + 2) * 64 + lane] = h;         // [previous batch (128) | own batch (128)]
                 }
             }
@@ -159,7 +155,6 @@ __device__ __forceinline__ void pipe_lds_trips(int nw64, int P, const PipePlan &
     const int glast = nw64 - 1;
     // two trips per iteration, the rows and bit words of one requested under the other's arithmetic, in registers
     // of their own (the single-trip form handed the next row over through four copies per trip)
-#if DLSM_TRIP_PRIO
 #define DLSM_LDS_PRIO_STEP()                                                                              \
         if (--left == 0) {                                                                                \
             left = quarter;                                                                               \
@@ -168,9 +163,6 @@ __device__ __forceinline__ void pipe_lds_trips(int nw64, int P, const PipePlan &
             else __builtin_amdgcn_s_setprio(0);                                                           \
             --level;                                                                                      \
         }
-#else
-#define DLSM_LDS_PRIO_STEP()
-#endif
 #define DLSM_LDS_NEXT(G_) { ++G_; if (G_ == pl.glo) G_ += pl.nwin; }
     int i = 0;
     for (; i + 1 < pl.r; i += 2) {
@@ -245,7 +237,7 @@ __device__ __forceinline__ void pipe_xserve_request(const PipeLds &a, int l, int
     const unsigned long long *pmg = (const unsigned long long *)(a.acc + moff);
     xs.m = __builtin_nontemporal_load(pmg + (lane >> 5));
     const uint32_t hoff = (uint32_t)((((b & 1) * a.T + t) * PP_B + k) * (2 * PP_B) + 2 * lane);
-    xs.v = *(const double2 *)(a.Hd + hoff);                              // factors of window nodes 2 lane, 2 lane + 1
+    xs.v = *(const double2 *)(a.H + hoff);                              // factors of window nodes 2 lane, 2 lane + 1
     xs.slot = a.xprod + (uint32_t)row;
     xs.on = true;
 }
@@ -265,13 +257,13 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
     // the launch's arguments in one piece (PipeLds): the pointers and scalars below are 128 contiguous bytes of the
     // kernel's argument block, pinned here so that they are requested together by the first instructions
     PipeLds a;
-    a.X = pb.lds.X; a.ybits = pb.lds.ybits; a.prop = pb.lds.prop; a.full0 = pb.lds.full0; a.Hd = pb.lds.Hd;
+    a.X = pb.lds.X; a.ybits = pb.lds.ybits; a.prop = pb.lds.prop; a.full0 = pb.lds.full0; a.H = pb.lds.H;
     a.acc = pb.lds.acc; a.consts = pb.lds.consts; a.xprod = pb.lds.xprod;
     a.T = pb.lds.T; a.N = pb.lds.N; a.W = pb.lds.W; a.squared = pb.lds.squared; a.parts = pb.lds.parts;
     a.nbat = pb.lds.nbat; a.lds_cap = pb.lds.lds_cap; a.xserve = pb.lds.xserve;
     a.beE = pb.lds.beE; a.beO = pb.lds.beO; a.nbE = pb.lds.nbE; a.nbO = pb.lds.nbO; a.nslE = pb.lds.nslE;
     a.nslO = pb.lds.nslO; a.xstride = pb.lds.xstride; a.nsl_magic = pb.lds.nsl_magic;
-    asm volatile("" :: "s"(a.X), "s"(a.ybits), "s"(a.prop), "s"(a.full0), "s"(a.Hd), "s"(a.acc), "s"(a.consts), "s"(a.xprod));
+    asm volatile("" :: "s"(a.X), "s"(a.ybits), "s"(a.prop), "s"(a.full0), "s"(a.H), "s"(a.acc), "s"(a.consts), "s"(a.xprod));
     asm volatile("" :: "s"(a.T), "s"(a.N), "s"(a.W), "s"(a.squared), "s"(a.parts), "s"(a.nbat), "s"(a.lds_cap), "s"(a.xserve),
                  "s"(a.beE), "s"(a.beO), "s"(a.nbE), "s"(a.nbO), "s"(a.nslE), "s"(a.nslO), "s"(a.xstride), "s"(a.nsl_magic));
     const int T = a.T, N = a.N;
@@ -315,9 +307,7 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
         const uint32_t tN = (uint32_t)t * (uint32_t)N;
         const double *Xt = a.X + (size_t)tN * D;
         const double *props = a.prop + (size_t)tN * PW;
-#if DLSM_TRIP_PRIO
         __builtin_amdgcn_s_setprio(3);
-#endif
         // ---- every request of the round, then the LDS stores, then ONE barrier ----------------------------
         double2 tabv = make_double2(0.0, 0.0);
         if (first) tabv = ((const double2 *)c_exp2_tab11)[tid];          // 1024 threads x 2 entries
@@ -366,7 +356,7 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
         const unsigned long long *yrow = (const unsigned long long *)(a.ybits + (size_t)(tN + (uint32_t)jk) * (uint32_t)a.W);
         // (a part without trips - more parts than trips at tiny N - names a trip behind the row: clamped, unused)
         const unsigned long long ym0 = scalar_load_u64(yrow + min(pl.trip(0, p, P), (a.W >> 1) - 1));
-        double *hrow = a.Hd + (size_t)((uint32_t)(((be & 1) * T + t) * PP_B + min(k, nb - 1)) * (uint32_t)(2 * PP_B));     // (< 2^31 doubles: T < 128)
+        double *hrow = a.H + (size_t)((uint32_t)(((be & 1) * T + t) * PP_B + min(k, nb - 1)) * (uint32_t)(2 * PP_B));     // (< 2^31 doubles: T < 128)
         if (STAMP_PROLOGUE_PROBE) { DLSM_STAMP(st, 1, (double)lane) }     // (the probe: slot 1 = requests issued, slot 2 = at the barrier)
         if (first) ((double2 *)sTab)[tid] = tabv;
         if (s < nst) stage_store(s);

@@ -35,21 +35,14 @@
 // them, so a wavefront spends one division where the additive form needs a
 // float64 log per node part and per H entry (each executed by all 64 lanes); the
 // resolver pays one exp per node instead.  (A node whose log-ratio is beyond +-700 - exp would
-// saturate - is resolved in the log domain, with the logs of its H factors: pipe_resolve.)
+// saturate - is resolved in the log domain, with the logs of its H factors.)
 #pragma once
 #include "kernels_spec_sweep.hpp"
 #include "kernel_stamps.hpp"
 
 namespace dlsm {
 
-// 1: the last wavefront of a SIMD hands its first-round H entries to the first one (pipe_item_finish).  Under
-// oldest-first issue this measured slower (10.77 against 10.54 us); with the items advancing together
-// (DLSM_TRIP_PRIO) the first wavefront of a SIMD still leaves ~1.8 us before the last one, whose entry is the
-// launch's tail: 9.82 -> 9.58 us per launch, C2 4565 -> 4660 it/s
-#ifndef DLSM_H_SHIFT
-#define DLSM_H_SHIFT 1
-#endif
-// 1: a wavefront's issue priority falls as its item advances (s_setprio 3 for the first quarter of the
+// A wavefront's issue priority falls as its item advances (s_setprio 3 for the first quarter of the
 // prefetched trips .. 0 for the last).  The arbiter serves a SIMD's ready wavefronts oldest first: its four
 // items ran nearly one after the other (first trip done after 0.7 / 1.4 / 3.0 / 4.5 us, exit after 3.8 / 5.3 /
 // 7.1 / 8.6: profiles/r04_h_entry_ablation.md), and the youngest ran its tail alone, with nobody to fill the
@@ -60,18 +53,11 @@ namespace dlsm {
 // 9.90 us, 4570 it/s.  (The table's fill + barrier moved behind the item's operand requests, so that the two
 // round trips overlap: 10.65 us - the barrier then holds all sixteen wavefronts until the last one's operands
 // have arrived; dropped.)
-#ifndef DLSM_TRIP_PRIO
-#define DLSM_TRIP_PRIO 1
-#endif
-#if DLSM_TRIP_PRIO
 #define DLSM_TRIP_PRIO_STEP(U_)                                                                \
         if ((U_) == 0) __builtin_amdgcn_s_setprio(3);                                          \
         else if ((U_) == (PP_NPRE * 1) / 4) __builtin_amdgcn_s_setprio(2);                     \
         else if ((U_) == (PP_NPRE * 2) / 4) __builtin_amdgcn_s_setprio(1);                     \
         else if ((U_) == (PP_NPRE * 3) / 4) __builtin_amdgcn_s_setprio(0);
-#else
-#define DLSM_TRIP_PRIO_STEP(U_)
-#endif
 constexpr int PP_THREADS = 1024;
 constexpr int PP_WAVES = PP_THREADS / 64;
 constexpr int PP_B = 128;               // nodes per batch (two 64-lane halves)
@@ -86,7 +72,7 @@ constexpr int PP_ACC_MASK = PP_B + 4;
 // kernel argument where it is first used - a dozen scalar loads, each with a wait of its own, in a prologue that
 // the four wavefronts of a SIMD issue one after the other).
 struct PipeLds {
-    const double *X; const uint32_t *ybits; double *prop; double *full0; double *Hd; int32_t *acc; double *consts;
+    const double *X; const uint32_t *ybits; double *prop; double *full0; double *H; int32_t *acc; double *consts;
     double *xprod;
     int T, N, W, squared, parts, nbat, lds_cap, xserve;
     // per launch: the batch evaluated / its nodes / the active slices (even and odd slices); evaluator workgroup e
@@ -97,23 +83,35 @@ struct PipeLds {
 };
 static_assert(sizeof(PipeLds) == 256, "PipeLds: two 64-byte halves of scalars and the plan table");
 
-// G batches are resolved (and G evaluated) per launch.  Batch b is evaluated while the batches
-// from ws(b) = G (b / G - 1) on are still unresolved - its WINDOW: G = 1: the previous batch;
-// G = 2: two or three batches - and everything produced per batch lives in slot b mod 2G.
+// One batch is resolved (and the next one evaluated) per launch.  Batch b is evaluated while batch b - 1 is still
+// unresolved - its WINDOW: the previous batch, if any - and everything produced per batch lives in slot b & 1.
+//
+// The H factors of a (slot, slice) - exp(H[k][m]): what node m's acceptance does to the ratio of a later node k -
+// are PP_H_SLICE doubles of PipeBuf::H, filed in one of two forms:
+//   rows   (the exact-likelihood models; written by pipe_h_entry and pipe_lds_trips, read by row_resolve and
+//          pipe_xserve_request): [2][T][PP_B][window PP_B | own PP_B], one row of PP_H_ROW factors per later node
+//          k - those of its window's nodes, then those of the earlier nodes of its own batch
+//   dense case-control (written by pipe_cc_writeout, read by pipe_resolve_ccdense): blocks indexed [m][k], the
+//          diagonal ones (m and k > m in the batch) as [2][T][PP_B][PP_B] at H, the cross ones (m in the window)
+//          as [2][T][PP_B][PP_B] behind them, at H + pipe_h_cc_cross(T)
+constexpr int PP_H_ROW = 2 * PP_B;
+constexpr int PP_H_SLICE = PP_B * PP_H_ROW;
+__host__ __device__ constexpr size_t pipe_h_doubles(int T) { return (size_t)2 * T * PP_H_SLICE; }
+// dense case-control form: the cross blocks start behind the [2][T] diagonal blocks
+__host__ __device__ constexpr size_t pipe_h_cc_cross(int T) { return (size_t)2 * T * PP_B * PP_B; }
+static_assert(2 * PP_B * PP_B == PP_H_SLICE, "a diagonal and a cross block fill the (slot, slice)'s share of H");
 struct PipeBuf {
     double *prop;    // [T][N][2D + 2] : x1[D], u, (unused), x0[D] (snapshot)
-    double *full0;   // [2G][T][PP_B][parts][2] : (sum of linear terms, ratio of products)
-    double *Hd;      // [2G][T][PP_B][PP_B] : Hd[m][k], k > m, both in the batch: the FACTOR
-                     //                      exp(H[k][m]) of node m's acceptance
-    double *Hx;      // [2G][T][xr][PP_B] : Hx[m][k], m the m-th node of the window's earlier batches
-    int32_t *acc;    // [T][2G][PP_ACC] : count, accepted nodes of the batch in that slot, their masks
+    double *full0;   // [2][T][PP_B][parts][2] : (sum of linear terms, ratio of products)
+    double *H;       // pipe_h_doubles(T) : the H factors, by rows or as dense case-control blocks (above)
+    LsmDeviceState *lsm_draw;   // not NULL: the proposal pass also draws the intercept proposal
+                     // (the fourth pointer: the fields behind it keep their 16-byte alignment in the kernel's argument
+                     // block.  8 bytes earlier the compiler groups their scalar loads differently, and the directed
+                     // evaluator, at the SGPR limit, came out 60 instructions longer: profiles/pipe_one_batch_refactor.md)
+    int32_t *acc;    // [T][2][PP_ACC] : count, accepted nodes of the batch in that slot, their masks
     double *consts;  // [2] : E = exp(sum of intercepts), flush interval
     const int32_t *nctrl;   // case-control: valid controls per (t, i, direction)
     int parts, per, nbat;
-    int G, xr;       // batches per launch; rows of an Hx block = (2G - 1) PP_B
-    // (ProposeBuf's flag words of the persistent form removed in round 5: always null / 0 here)
-    int32_t *sync; int nsync, queue0;
-    LsmDeviceState *lsm_draw;   // not NULL: the proposal pass also draws the intercept proposal
     PipeLds lds;     // kernels_pipe_lds.hpp: the evaluators' arguments (filled by the host per launch)
     // the cross products by the evaluators (kernels_pipe_lds.hpp, pipe_xserve): slot [t][k] holds PP_XP_EMPTY
     // until the wavefront that serves row k of slice t has stored prod_{m accepted} Hx[k][m]; the row's owner in
@@ -122,13 +120,12 @@ struct PipeBuf {
     int lds_eval;    // undirected model: the evaluators of kernels_pipe_lds.hpp (rows staged in LDS, interleaved
                      // parts, H factors inside the trips); 0: pipe_eval_item
 };
+// (the argument loads of the evaluators keep their grouping only while the fields behind lsm_draw stay where they are)
+static_assert(offsetof(PipeBuf, acc) % 16 == 0 && offsetof(PipeBuf, lds) % 16 == 8, "PipeBuf: see lsm_draw");
 constexpr unsigned long long PP_XP_EMPTY = 0x7FF8C0DE5EED0002ull;     // a NaN payload no arithmetic produces
 constexpr int PP_ERR_XSERVE = 1 << 29;          // sticky error word: a resolver ran out of its poll budget
-// first batch of the window of batch b
-__host__ __device__ __forceinline__ int pipe_window_start(int b, int G) {
-    const int ws = G * (b / G - 1);
-    return ws > 0 ? ws : 0;
-}
+// the window of batch b starts with the batch before it, if any
+__host__ __device__ __forceinline__ int pipe_window_start(int b) { return b > 0 ? b - 1 : 0; }
 
 // The proposal pass of a sweep, as pieces: it runs as its own launch (k_pipe_propose) or, inside
 // the device-resident loops, as extra workgroups of the previous iteration's last launch
@@ -166,7 +163,7 @@ __device__ __forceinline__ void pipe_propose_row_from(const ChainView &c, const 
     make_proposal<D>(c, iter, t, j, x0, c.step[(size_t)t * N + j], x1, logu);
     double *pr = pb.prop + ((size_t)t * N + j) * (2 * D + 2);
 #pragma unroll
-    for (int d = 0; d < D; ++d) { pr[d] = x1[d]; pr[D + 2 + d] = x0[d]; }
+    for (int d = 0; d < D; ++d) pr[d] = x1[d];
     {   // the uniform itself (same draw as make_proposal's log u)
         double u0, u1;
         philox_uniform2(c.seed, (uint32_t)j, (uint32_t)t, iter,
@@ -174,6 +171,8 @@ __device__ __forceinline__ void pipe_propose_row_from(const ChainView &c, const 
         pr[D] = u0;
     }
     pr[D + 1] = 0.0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) pr[D + 2 + d] = x0[d];     // the snapshot, in the row's order
 }
 
 // workgroup `fb` of ceil(N / 256) T, 256 threads
@@ -183,26 +182,12 @@ __device__ __forceinline__ void pipe_propose_rows(const ChainView &c, const Prop
     const int N = c.N, nbx = (N + 255) / 256;
     const int t = fb / nbx;
     const int j = (fb - t * nbx) * 256 + tid;
-    if (pb.sync) {
-        const int flat = fb * 256 + tid;
-        if (flat < pb.nsync) pb.sync[(size_t)flat * 16] = flat == 0 ? pb.queue0 : 0;
-    }
     if (j >= N) return;
     // valid for the whole sweep: X[t, j] and its step size change only at step (t, j)
-    double x0[D], x1[D], logu;
+    double x0[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) x0[d] = c.X[((size_t)t * N + j) * D + d];
-    make_proposal<D>(c, iter, t, j, x0, c.step[(size_t)t * N + j], x1, logu);
-    double *pr = pb.prop + ((size_t)t * N + j) * (2 * D + 2);
-#pragma unroll
-    for (int d = 0; d < D; ++d) { pr[d] = x1[d]; pr[D + 2 + d] = x0[d]; }
-    {   // the uniform itself (same draw as make_proposal's log u)
-        double u0, u1;
-        philox_uniform2(c.seed, (uint32_t)j, (uint32_t)t, iter,
-                        stream_word(c.chain, STREAM_SWEEP_UNIFORM), u0, u1);
-        pr[D] = u0;
-    }
-    pr[D + 1] = 0.0;
+    pipe_propose_row_from<D>(c, pb, iter, t, j, x0);
 }
 
 template <int D>
@@ -212,7 +197,7 @@ __global__ __launch_bounds__(256) void k_pipe_propose(ChainView c, PipeBuf pb, I
         pipe_propose_consts(c, pb.consts, c.intercept);
         if (pb.lsm_draw) pipe_propose_intercept(c, pb.lsm_draw, c.intercept, ir.get());
     }
-    const ProposeBuf nb{pb.prop, pb.consts, pb.sync, pb.nsync, pb.queue0, pb.lsm_draw};
+    const ProposeBuf nb{pb.prop, pb.consts, pb.lsm_draw};
     pipe_propose_rows<D>(c, nb, ir.get(), fb, (int)threadIdx.x);
 }
 
@@ -298,7 +283,7 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
     const int k = 64 * half + lane;
     const bool owner = wave < 2;
     const bool valid = k < nb;
-    const double *H = pb.Hd + ((size_t)bb * c.T + t) * PP_B * (2 * PP_B);
+    const double *H = pb.H + ((size_t)bb * c.T + t) * PP_H_SLICE;
     // ---- every load of the batch, at once ------------------------------------------------------
     // cross factors: node kx = tid / 8; trip u: window nodes 16 u + 2 jx, + 1 - the 8 lanes of a
     // node read one 128-byte line per trip
@@ -310,11 +295,7 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
     if (b > 0 && !served) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-#if defined(DLSM_X_RES) && (DLSM_X_RES & 1)      // measurement only: no cross block
-            const double2 v = make_double2(1.0, 1.0);
-#else
             const double2 v = coh_load2<false>(H, cr_off, (uint32_t)(16 * u * sizeof(double)));
-#endif
             cr[2 * u] = v.x; cr[2 * u + 1] = v.y;
         }
     }
@@ -329,11 +310,7 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
     const uint32_t blk_off = (uint32_t)((wave * (2 * PP_B) + PP_B + 2 * lane) * sizeof(double));
 #pragma unroll
     for (int u = 0; u < BLK_H; ++u)
-#if defined(DLSM_X_RES) && (DLSM_X_RES & 2)      // measurement only: no diagonal block
-        blk[u] = make_double2(1.0, 1.0);
-#else
         blk[u] = coh_load2<false>(H, blk_off, (uint32_t)(u * PP_WAVES * (2 * PP_B) * sizeof(double)));
-#endif
     // the owners' inputs (requested now, used once the blocks above have left their registers)
     double2 tv[4];
     double x1[D], x0[D], uk = 1.0, st = 0.0;
@@ -404,7 +381,7 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
     }
     // multiplicative domain: r = exp(log-ratio of node k), lu = its uniform draw.  A node whose
     // log-ratio is beyond +-700 (exp would saturate) is resolved in the log domain instead
-    // (pipe_resolve)
+    // (as in pipe_resolve_ccdense)
     double r = 0.0, lu = 0.0, lr = 0.0;
     bool sat = false;
     if (owner) {
@@ -560,27 +537,24 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
 #include "kernels_pipe_lds.hpp"
 namespace dlsm {
 
-// Launch l: even slices resolve batches G l .. G l + G - 1 and evaluate batches G (l + 1) ..;
-// odd slices run one launch behind (batches outside [0, nbat) do nothing).
+// Launch l: even slices resolve batch l and evaluate batch l + 1; odd slices run one launch behind (batches
+// outside [0, nbat) do nothing).
 // Workgroups [0, T) are the resolvers, the rest evaluate one item per wavefront and round.
 // MODEL = PIPE_UNDIRECTED_LONG: the undirected model with parts longer than the prefetch
 constexpr int PIPE_UNDIRECTED_LONG = 3;
 
 template <int D, int MODEL_, int G = 1>
 __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf pb, int l) {
+    // (the benchmark's roofline, profiles/ and six rounds of stored profiler output name this kernel k_pipe_step<2,0,1>)
+    static_assert(G == 1, "one batch per launch: the third parameter only keeps the kernel's symbol");
     constexpr int MODEL = MODEL_ == PIPE_UNDIRECTED_LONG ? DLSM_UNDIRECTED : MODEL_;
     constexpr bool TP = MODEL_ != DLSM_UNDIRECTED;
     extern __shared__ __attribute__((aligned(16))) double pp_sH[];      // 128 x PR_LD
     __shared__ double sPart[PP_WAVES * 64];
     __shared__ unsigned long long sMask[2][2];
-    __shared__ int sPrev[3 * PP_B];
-    __shared__ int sOwn[PP_B + 1];
-    __shared__ unsigned char sSat[PP_B];
     const int T = c.T;
-    // one batch per launch, exact likelihoods: the H blocks by rows and their resolver (row_resolve)
-    constexpr bool ROWS = G == 1 && MODEL != DLSM_DIRECTED_CASE_CONTROL;
     const int bx = (int)blockIdx.x;
-    const bool grid3 = MODEL_ == DLSM_UNDIRECTED && G == 1 && pb.lds_eval && (int)gridDim.x > T;    // kernels_pipe_lds.hpp's evaluators
+    const bool grid3 = MODEL_ == DLSM_UNDIRECTED && pb.lds_eval && (int)gridDim.x > T;    // kernels_pipe_lds.hpp's evaluators
     if (grid3) {
         if (bx >= T) {
             Stamps<PIPE_ITEM_T> first;                  // (read by the item's record, never flushed itself)
@@ -591,26 +565,23 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
     }
     if (bx < T) {
         const int t = bx;
-        if (ROWS) {
-            __shared__ double sCross[PP_B];
-            __shared__ unsigned long long sSatMask[2];
-            __shared__ double sTab[EXPTAB_N];
-            const int b = l - (t & 1);
-            const bool served = pb.xserve != 0 && grid3;                  // (both sides decide by the same rule)
-            if (l == -1 && threadIdx.x < PP_B)                            // the sweep's first launch: every slot empty
-                pb.xprod[(size_t)t * PP_B + threadIdx.x] = __longlong_as_double((long long)PP_XP_EMPTY);
+        const int b = l - (t & 1);
+        if (MODEL == DLSM_DIRECTED_CASE_CONTROL) {
+            __shared__ int sPrev[PP_B];
+            __shared__ unsigned char sSat[PP_B];
             if (b < 0 || b >= pb.nbat) return;
-            row_resolve<D>(c, pb, b, t, pp_sH, sPart, sMask, sCross, sSatMask, sTab, served, Stamps<PIPE_RES_T>(l + 1, t));
+            pipe_resolve_ccdense<D>(c, pb, b, t, pp_sH, sPart, sMask, sPrev, sSat, Stamps<PIPE_RES_T>(l + 1, t));
             return;
         }
-        bool own_prev = false;
-        for (int g = 0; g < G; ++g) {
-            const int b = G * (l - (t & 1)) + g;
-            if (b < 0 || b >= pb.nbat) continue;
-            if (own_prev) __syncthreads();          // the LDS of the batch before is free again
-            pipe_resolve<D, G>(c, pb, b, t, pp_sH, sPart, sMask, sPrev, sSat, sOwn, own_prev, Stamps<PIPE_RES_T>(l + 1, t));
-            own_prev = true;
-        }
+        // exact likelihoods: the H factors by rows and their resolver
+        __shared__ double sCross[PP_B];
+        __shared__ unsigned long long sSatMask[2];
+        __shared__ double sTab[EXPTAB_N];
+        const bool served = pb.xserve != 0 && grid3;                  // (both sides decide by the same rule)
+        if (l == -1 && threadIdx.x < PP_B)                            // the sweep's first launch: every slot empty
+            pb.xprod[(size_t)t * PP_B + threadIdx.x] = __longlong_as_double((long long)PP_XP_EMPTY);
+        if (b < 0 || b >= pb.nbat) return;
+        row_resolve<D>(c, pb, b, t, pp_sH, sPart, sMask, sCross, sSatMask, sTab, served, Stamps<PIPE_RES_T>(l + 1, t));
         return;
     }
     // (the undirected model's evaluators are kernels_pipe_lds.hpp's above; when their rows do not fit the LDS or
@@ -621,7 +592,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
     DLSM_STAMP(first, 0, (double)threadIdx.x)                       // the wavefront's first instruction
     const int lane = threadIdx.x & 63;
     const int nE = (T + 1) / 2, nO = T / 2;
-    const int beE = G * (l + 1), beO = G * l;        // first batch evaluated (even / odd slices)
+    const int beE = l + 1, beO = l;                  // the batch evaluated (even / odd slices)
     const int nbE = (beE >= 0 && beE < pb.nbat) ? min(PP_B, c.N - beE * PP_B) : 0;
     const int nbO = (beO >= 0 && beO < pb.nbat) ? min(PP_B, c.N - beO * PP_B) : 0;
     if (MODEL == DLSM_DIRECTED_CASE_CONTROL) {
@@ -650,12 +621,10 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
         }
         return;
     }
-    // items ordered (part, active slice, k) with 128 k-slots per slice, so that an item id
+    // items ordered (part, active slice, k) with PP_B k-slots per slice, so that an item id
     // decodes with a shift, a mask and one small quotient (no integer divisions)
-    // (a launch's first batch exists whenever any of its G batches does)
-    constexpr int gsh = G == 2 ? 8 : 7;                // k-slots per slice: G * 128
     const int nslE = nbE > 0 ? nE : 0, nslO = nbO > 0 ? nO : 0, nsl = nslE + nslO;
-    const int nitems = (pb.parts * nsl) << gsh;
+    const int nitems = (pb.parts * nsl) << 7;
     const float inv_nsl = 1.0f / (float)max(nsl, 1);
     // the evaluators' table of 2^(j / 2048) (tab_exp11) in the dynamic LDS the resolvers use for H
     // (a barrier-free fill - every wavefront copying the table itself with global_load_lds_dwordx4 -
@@ -669,19 +638,17 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
         ((int)blockIdx.x - T) * PP_WAVES + (int)(threadIdx.x >> 6));
     for (int q = gw; q < nitems; q += nwaves) {
         const int k = q & (PP_B - 1);
-        const int g = (q >> 7) & (G - 1);
-        const int r = q >> gsh;
+        const int r = q >> 7;
         const int p = (int)(((float)r + 0.5f) * inv_nsl);        // r / nsl (r < 2^20)
         const int si = r - p * nsl;
         const bool odd = si >= nslE;
-        const int be = (odd ? beO : beE) + g;
+        const int be = odd ? beO : beE;
         const int nb = be < pb.nbat ? min(PP_B, c.N - be * PP_B) : 0;
         if (k >= nb) continue;
         const int t = odd ? 2 * (si - nslE) + 1 : 2 * si;
-        constexpr int IM = MODEL == DLSM_DIRECTED_CASE_CONTROL ? DLSM_DIRECTED : MODEL;
         PipeItemPre<D> pre;
-        pipe_item_prologue<D, IM>(c, pb, be, t, k, p, lane, pre);
-        pipe_eval_item<D, IM, TP, G>(c, pb, be, nb, t, k, p, lane, pp_sH, pre, Stamps<PIPE_ITEM_T>(l + 1, gw));
+        pipe_item_prologue<D, MODEL>(c, pb, be, t, k, p, lane, pre);
+        pipe_eval_item<D, MODEL, TP>(c, pb, be, nb, t, k, p, lane, pp_sH, pre, Stamps<PIPE_ITEM_T>(l + 1, gw));
         // (slot 4, "H operands here", gives way to the wavefront's first stamp in the kernel: both evaluators
         // on one time axis)
         Stamps<PIPE_ITEM_T> item(l + 1, q);
@@ -702,8 +669,7 @@ struct PipePostRide { const double *xref; IterRef ir; double *rec; int nwg, jl, 
 template <int D>
 __device__ __forceinline__ void pipe_last_ride_wg(const ChainView &c, const PipeBuf &pb, int l,
                                                   const PipePostRide &pr, int bx, double *pp_sH,
-                                                  double *sPart, unsigned long long (*sMask)[2],
-                                                  int *sPrev, int *sOwn, unsigned char *sSat) {
+                                                  double *sPart, unsigned long long (*sMask)[2]) {
     const int T = c.T;
     if (bx < T) {
         // The rows this launch is still moving (nodes i >= jl of this slice) and the difference terms
@@ -756,10 +722,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_last_ride(ChainView c, Pipe
     extern __shared__ __attribute__((aligned(16))) double pp_sH[];      // 128 x 128
     __shared__ double sPart[PP_WAVES * 64];
     __shared__ unsigned long long sMask[2][2];
-    __shared__ int sPrev[3 * PP_B];
-    __shared__ int sOwn[PP_B + 1];
-    __shared__ unsigned char sSat[PP_B];
-    pipe_last_ride_wg<D>(c, pb, l, pr, (int)blockIdx.x, pp_sH, sPart, sMask, sPrev, sOwn, sSat);
+    pipe_last_ride_wg<D>(c, pb, l, pr, (int)blockIdx.x, pp_sH, sPart, sMask);
 }
 
 }  // namespace dlsm

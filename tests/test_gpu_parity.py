@@ -130,7 +130,7 @@ def test_directed_large_exponent_corner(eng):
         # sweeps: the pipelined form against the per-slice kernel (same decisions).  This corner
         # drives log-ratios of single-node moves beyond +-700, where exp() of the pipelined form's
         # multiplicative accept test would saturate: those nodes are resolved in the log domain
-        # (pipe_resolve), so the two forms keep agreeing sweep after sweep.
+        # (row_resolve), so the two forms keep agreeing sweep after sweep.
         c.set_prior_random_walk(2.0, 0.1)
         big = 0
         res47 = {}
@@ -449,6 +449,16 @@ def test_sweep_speculative_batches_case_control(eng, T, N, C, density, prior, al
     corrections as per-node lists (batches of 512: one or two batches at these sizes)"""
     _sweep_case(eng, 'case_control', prior, T=T, N=N, D=2, n_sweeps=3, algo=algo,
                 scale=0.05, cc_C=C, density=density)
+
+
+@pytest.mark.parametrize('prior', ['rw', 'mix'])
+@pytest.mark.parametrize('T,N,D', [(1, 129, 2), (2, 257, 3), (3, 130, 1), (2, 260, 4)])
+def test_sweep_pipelined_case_control_dense_resolver(eng, T, N, D, prior):
+    """algo 4's dense case-control resolver (kernels_pipe_ccdense.hpp) where the cases above do not take it:
+    T = 1, N = 129 has no odd slices and a second batch of one node whose window is a full batch; T = 2, N = 257
+    has three batches, so a batch slot is reused, the odd slice runs one launch behind and the last batch is ragged;
+    d = 1, 3, 4 are the other dimensions of the register plan"""
+    _sweep_case(eng, 'case_control', prior, T=T, N=N, D=D, n_sweeps=3, algo=4, scale=0.05, cc_C=20, density=0.05)
 
 
 @pytest.mark.parametrize('T,N,C,density,prior', [(3, 2300, 12, 0.004, 'rw'), (2, 1025, 30, 0.01, 'mix'),

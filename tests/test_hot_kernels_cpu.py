@@ -63,11 +63,12 @@ def test_matrix_core_label_kernel_is_built_for_the_sizes_that_stay_in_registers(
 # Every kernel of the library outside the list above: scratch memory is tolerated only where it is known, off
 # the benchmark configurations' paths, and may not grow (round-4 verdict, weak 10; round 5 removed the
 # two-batch and persistent sweeps and cleared every k_ccpipe_step / k_loglik_casecontrol instantiation).
+# (k_pipe_step<D,MODEL,1>: the third parameter is always 1 - it only keeps the symbol the stored profiles name.)
 # bytes of private segment per thread at HEAD:
 KNOWN_SCRATCH = {
     # d = 3 / 4 instantiations of the pipelined sweep (resolver: the blocks' 64 registers + 8 d of the owners)
     'k_pipe_step<3,1,1>': 12, 'k_pipe_step<3,2,1>': 52, 'k_pipe_step<4,0,1>': 20, 'k_pipe_step<4,3,1>': 52,
-    'k_pipe_step<4,1,1>': 60, 'k_pipe_step<4,2,1>': 84, 'k_pipe_last_ride<4>': 36,
+    'k_pipe_step<4,1,1>': 60, 'k_pipe_step<4,2,1>': 68, 'k_pipe_last_ride<4>': 36,
     # d = 2: the dense case-control form (512 <= N < 2048).  (Round 6: the fallback for parts longer than the prefetch,
     # k_pipe_step<2,3,1>, is clean - its rare-path exponential is the table's, as the LDS evaluators'.)
     'k_pipe_step<2,2,1>': 28,
@@ -92,10 +93,10 @@ KNOWN_SCRATCH = {
     # two or three prefetched trips of d registers each no longer fit the 128 of a 1024-thread workgroup; 2910 it/s at
     # d = 5, 1465 at d = 8 against 1660 / 1330 for the speculative sweep - DESIGN.md 9)
     'k_pipe_last_ride<5>': 76, 'k_pipe_last_ride<6>': 148, 'k_pipe_last_ride<7>': 300, 'k_pipe_last_ride<8>': 500,
-    'k_pipe_step<5,0,1>': 72, 'k_pipe_step<5,1,1>': 108, 'k_pipe_step<5,2,1>': 108, 'k_pipe_step<5,3,1>': 84,
+    'k_pipe_step<5,0,1>': 72, 'k_pipe_step<5,1,1>': 108, 'k_pipe_step<5,2,1>': 100, 'k_pipe_step<5,3,1>': 84,
     'k_pipe_step<6,0,1>': 116, 'k_pipe_step<6,1,1>': 180, 'k_pipe_step<6,2,1>': 164, 'k_pipe_step<6,3,1>': 144,
-    'k_pipe_step<7,0,1>': 172, 'k_pipe_step<7,1,1>': 224, 'k_pipe_step<7,2,1>': 208, 'k_pipe_step<7,3,1>': 200,
-    'k_pipe_step<8,0,1>': 212, 'k_pipe_step<8,1,1>': 312, 'k_pipe_step<8,2,1>': 248, 'k_pipe_step<8,3,1>': 240,
+    'k_pipe_step<7,0,1>': 172, 'k_pipe_step<7,1,1>': 224, 'k_pipe_step<7,2,1>': 204, 'k_pipe_step<7,3,1>': 200,
+    'k_pipe_step<8,0,1>': 212, 'k_pipe_step<8,1,1>': 312, 'k_pipe_step<8,2,1>': 244, 'k_pipe_step<8,3,1>': 240,
     # ... and the sparse case-control sweep there (two chunks of records and proposals of d doubles in flight)
     'k_ccpipe_step<5>': 24, 'k_ccpipe_step<6>': 72, 'k_ccpipe_step<7>': 136, 'k_ccpipe_step<8>': 168,
 }
