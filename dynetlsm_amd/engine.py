@@ -949,6 +949,50 @@ class Chain(object):
             hist_k.ctypes.data_as(_lib.c_u64_p), _p(node_k), _p(pw) if want_pointwise else None))
         return (totals, hist_k, node_k, pw) if want_pointwise else (totals, hist_k, node_k)
 
+    # -- posterior edge probabilities (no reference counterpart) ----------------------------------
+    def proba_accumulate(self, bits, Xs, intercepts, radii, level, mask=None, n_bins=20,
+                         width_edges=(0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5), pointwise=False):
+        """Mean, standard deviation (ddof 1) and the equal-tailed credible interval at ``level`` of the edge
+        probability of every dyad over the S >= 2 samples (arguments as ``score_accumulate``; ``radii`` None
+        for undirected chains), and the calibration of the posterior mean against the packed network ``bits``
+        over the dyads that ``mask`` does not exclude, in one pass on the device (csrc/kernels_proba.hpp; the
+        definition: include/dynetlsm_hip.h).  Returns uint64 tables - ``calib`` (T, n_bins, 3): scored dyads,
+        those with y = 1 and the sum of the mean in units of 2^-32 per bin of the mean; ``brier`` (T,):
+        sum (y - mean)^2 in the same units; ``node_sums`` (T, N, 2): the mean of dyad (i, j) added to slot 0
+        of i and slot 1 of j; ``hist_width`` (T, len(width_edges) + 1): the bin of upper - lower is the
+        number of edges <= it - and, with ``pointwise``, (T, N, N, 4) = (mean, sd, lower, upper) of every
+        dyad (undirected: i < j filled, the rest 0), else None."""
+        level = float(level)
+        if not 0.0 < level < 1.0:
+            raise ValueError('level must lie in (0, 1), got %r' % (level,))
+        n_bins = int(n_bins)
+        if not 1 <= n_bins <= 64:
+            raise ValueError('n_bins must be between 1 and 64, got %d' % n_bins)
+        we = np.ascontiguousarray(np.ravel(width_edges), dtype=np.float64)
+        if we.size > 16:
+            raise ValueError('at most 16 edges per histogram')
+        if not np.all(np.isfinite(we)) or np.any(np.diff(we) <= 0):
+            raise ValueError('width_edges must be finite and ascending')
+        bits = self._packed(bits, 'bits')
+        if mask is not None:
+            mask = self._packed(mask, 'mask')
+        if np.shape(Xs)[0] < 2:
+            raise ValueError('needs at least two samples (the standard deviation has ddof = 1)')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii)
+        calib = np.zeros((self.T, n_bins, 3), dtype=np.uint64)
+        brier = np.zeros(self.T, dtype=np.uint64)
+        node_sums = np.zeros((self.T, self.N, 2), dtype=np.uint64)
+        hist_width = np.zeros((self.T, we.size + 1), dtype=np.uint64)
+        pw = np.zeros((self.T, self.N, self.N, 4)) if pointwise else None
+        u64 = _lib.c_u64_p
+        self._ck(self._L.dlsm_proba_accumulate(
+            self._h, bits.ctypes.data_as(_lib.c_u32_p),
+            mask.ctypes.data_as(_lib.c_u32_p) if mask is not None else None, _p(Xs), _p(b),
+            _p(r) if r is not None else None, int(S), C.c_double(level), n_bins, _p(we) if we.size else None,
+            int(we.size), calib.ctypes.data_as(u64), brier.ctypes.data_as(u64), node_sums.ctypes.data_as(u64),
+            hist_width.ctypes.data_as(u64), _p(pw) if pointwise else None))
+        return calib, brier, node_sums, hist_width, pw
+
     # -- multi-step posterior predictive forecasts (the reference: one step, undirected, on the host) ----
     def forecast_paths(self, X0, intercepts, radii=None, z0=None, trans=None, mu=None, sigma=None, lmbda=None,
                        sigma_sq=0.0, horizon=1, seed=0, first_index=0, batch=0, want_paths=False,

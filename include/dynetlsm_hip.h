@@ -515,6 +515,38 @@ int dlsm_loo_accumulate(dlsm_chain *h, const uint32_t *bits, const double *Xs, c
                         const double *radii, int S, const double *k_edges, int n_edges, double *totals,
                         uint64_t *hist_k, double *node_k_max, double *pointwise);
 
+/* ---- posterior edge probabilities (credible intervals, calibration) ------ */
+/* No reference counterpart.  For every dyad of the handle (undirected: t, i < j; directed and case-control: t,
+ * i != j; the same linear predictor eta, the same samples Xs S*T*N*D, intercepts S*2, radii S*N or NULL as
+ * dlsm_score_accumulate takes them), of p_s = expit(eta_s) over the S samples, in one pass:
+ *   mean = pbar, sd (ddof 1), and the equal-tailed interval at `level`: lower and upper are the quantiles at
+ *   alpha = (1 - level)/2 and at 1 - alpha as numpy's default defines them - linear interpolation of the order
+ *   statistics at position (S - 1) q.  Every dyad keeps its K = min(floor(alpha (S - 1)) + 2, S) smallest and its
+ *   K largest eta_s sorted in the LDS; expit is monotone, so the interpolation is on p.
+ * The dyads whose bit in `mask` (NULL, or T*N*W uint32 packed like the network `bits`; undirected handles: either of
+ * (i, j), (j, i)) is not set are scored against y = their bit of `bits`.  With fix(x) = llrint(x 2^32), over the
+ * scored dyads of time step t:
+ *   calib       T*n_bins*3 uint64: per bin b = min(floor(pbar n_bins), n_bins - 1) the dyads, those with y = 1, and
+ *               sum fix(pbar)
+ *   brier       T uint64: sum fix((y - pbar)^2)
+ *   node_sums   T*N*2 uint64: fix(pbar) of dyad (i, j) is added to slot 0 of node i and to slot 1 of node j (directed:
+ *               expected out- and in-degree; undirected: the dyads are i < j, and the two slots add up to the degree)
+ *   hist_width  T*(n_edges+1) uint64: dyads per bin of upper - lower over width_edges (bin of a value: the number of
+ *               edges <= it)
+ *   pointwise   NULL or T*N*N*4: (mean, sd, lower, upper) of every dyad (t, i, j), scored or not; undirected: i < j
+ *               filled, the rest 0
+ * Everything accumulated across dyads is an integer added with 64-bit atomics: the same call returns the same bits,
+ * whatever the order, with and without `pointwise`.  The fixed point costs at most half a unit of 2^-32 per dyad.
+ * S < 2, level outside (0, 1), n_bins outside 1..64, more than 16 edges -> DLSM_E_ARG; edges that are not finite and
+ * ascending, a set diagonal or padding bit of `bits`, a radius <= 0 -> DLSM_E_DATA.  2^31 or more dyads per time step
+ * (the sums stay below 2^63), samples that do not fit the device, or two columns of K values that do not fit the LDS
+ * (K <= 144) -> DLSM_E_LIMIT; for the samples and the columns the message names the largest S that fits at this
+ * level. */
+int dlsm_proba_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *mask, const double *Xs,
+                          const double *intercepts, const double *radii, int S, double level, int n_bins,
+                          const double *width_edges, int n_edges, uint64_t *calib, uint64_t *brier,
+                          uint64_t *node_sums, uint64_t *hist_width, double *pointwise);
+
 /* ---- multi-step posterior predictive forecasts --------------------------- */
 /* The reference has only the one-step undirected form (hdp_lpcm.py:555-626, drawn on the host).  One
  * trajectory of H future time steps per sample s, started at the sample's last time step X0 S*N*D:
