@@ -61,6 +61,7 @@ struct Knobs {
     bool cc_pass_records, cc_pass_rows;                 // DLSM_CC_PASS=records / =rows
     bool pipe_lds;                                      // DLSM_PIPE_LDS (0: off)
     int pipe_xserve, pipe_xbudget;                      // DLSM_PIPE_XSERVE (0 off, 2 forced), DLSM_PIPE_XBUDGET
+    bool pipe_wt, pipe_head_spread;                     // DLSM_PIPE_WT, DLSM_PIPE_HEAD_SPREAD (0: off)
     int cc_helpers, cc_helper_budget;                   // DLSM_CC_HELPERS (0 off, 2 forced), DLSM_CC_HELPER_BUDGET
     int spec_s;                                         // DLSM_SPEC_S: sub-batches of algo 3
     bool post_ride, post_fuse, tail_propose, hdp_head;  // DLSM_POST_RIDE, _POST_FUSE, _TAIL_PROPOSE, _HDP_HEAD (0: off)
@@ -75,6 +76,7 @@ Knobs read_knobs() {
     k.cc_pass_records = env_is("DLSM_CC_PASS", "records"); k.cc_pass_rows = env_is("DLSM_CC_PASS", "rows");
     k.pipe_lds = env_int("DLSM_PIPE_LDS", 1) != 0;
     k.pipe_xserve = env_int("DLSM_PIPE_XSERVE", 1); k.pipe_xbudget = env_int("DLSM_PIPE_XBUDGET", 1 << 22);
+    k.pipe_wt = env_int("DLSM_PIPE_WT", 1) != 0; k.pipe_head_spread = env_int("DLSM_PIPE_HEAD_SPREAD", 1) != 0;
     k.cc_helpers = env_int("DLSM_CC_HELPERS", 1); k.cc_helper_budget = env_int("DLSM_CC_HELPER_BUDGET", 1 << 22);
     k.spec_s = env_int("DLSM_SPEC_S", 2);
     k.post_ride = env_int("DLSM_POST_RIDE", 1) != 0; k.post_fuse = env_int("DLSM_POST_FUSE", 1) != 0;
@@ -1231,12 +1233,11 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
     const int N = h->N, T = h->T;
     const int nbat = (N + PP_B - 1) / PP_B;
     const bool cc = h->model == DLSM_DIRECTED_CASE_CONTROL;
-    int ne_wg = std::max(h->n_cu / 2, h->n_cu - T);
-    int parts = (int)((double)ne_wg * PP_WAVES / ((double)T * PP_B) + 0.5);
-    parts = std::max(1, std::min(parts, PP_MAXPARTS));
-    // (undirected model: the evaluators of kernels_pipe_lds.hpp take ONE round of items - a part less when
-    // rounding up would leave items for a second round)
-    if (h->model == DLSM_UNDIRECTED && parts > 1 && (long)parts * T * PP_B > (long)ne_wg * PP_WAVES) --parts;
+    int ne_wg = pipe_eval_workgroups(h->n_cu, T);
+    // (undirected model: the evaluators of kernels_pipe_lds.hpp take ONE round of items; pipe_plan.hpp states the
+    // rule, for its GPU-free test too)
+    static_assert(PP_MAXPARTS == 8, "pipe_parts clamps to PipeLds::plan's eight parts");
+    int parts = pipe_parts(ne_wg, T, h->model == DLSM_UNDIRECTED);
     if (cc) {           // CC_PARTS wavefronts per node, four nodes per workgroup round
         parts = CC_PARTS;
         ne_wg = std::min(ne_wg, (T * PP_B * CC_PARTS + PP_WAVES - 1) / PP_WAVES);
@@ -1280,14 +1281,17 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
     // forces it, 0 switches it off)
     // (a launch whose workgroups cannot cover the rows keeps the resolvers' own products)
     const int xserve_sweep = pb.lds_eval && pb.err != nullptr && T < 128 && alone_or_forced(kn.pipe_xserve, 0, 2);
-    pb.xserve = 0;
+    // what a launch hands to a later one goes out write-through (PP_F_WT): the LDS evaluators' rows and records and
+    // their resolvers' results, k_pipe_last_ride's included; DLSM_PIPE_WT=0 keeps the plain stores
+    const int wt_sweep = pb.lds_eval && kn.pipe_wt ? PP_F_WT : 0;
+    pb.flags = wt_sweep;
     ChainView v = h->view();
     {   // the evaluators' arguments (kernels_pipe_lds.hpp) in one piece
         PipeLds &a = pb.lds;
         a.X = v.X; a.ybits = v.ybits; a.prop = pb.prop; a.full0 = pb.full0; a.H = pb.H; a.acc = pb.acc;
         a.consts = pb.consts; a.xprod = pb.xprod;
         a.T = T; a.N = N; a.W = v.W; a.squared = v.squared; a.parts = parts; a.nbat = nbat;
-        a.lds_cap = pipe_lds_trip_cap((N + 63) / 64, parts); a.xserve = 0;
+        a.lds_cap = pipe_lds_trip_cap((N + 63) / 64, parts); a.flags = 0;
     }
     for (int nw = 1; nw <= 4; ++nw)
         for (int p = 0; p < PP_MAXPARTS; ++p)
@@ -1321,6 +1325,9 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
         // queue already, beside the previous iteration's conjugate draws: capi_hdp.hpp)
         if (l == -1 && !iter.ptr && h->carry.head_done_for == (long)iter.value) continue;
         if (sc.head_only && l >= 0) break;
+        if (l == -1) h->pipe_head_q = PP_WAVES;
+        // (a launch without the LDS evaluators serves nothing and spreads nothing: the resolvers' stores only)
+        pb.flags = wt_sweep;
         const bool any_eval = (l + 1 < nbat) || (T > 1 && l >= 0 && l < nbat);
         const int grid = T + (any_eval ? ne_wg : 0);
         const bool lng = !pb.lds_eval;       // (undirected model without the LDS evaluators: pipe_eval_item's pipelined trips)
@@ -1348,10 +1355,15 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
             a.nbO = (beO >= 0 && beO < nbat) ? std::min(PP_B, N - beO * PP_B) : 0;
             a.nslE = a.nbE > 0 ? nE : 0; a.nslO = a.nbO > 0 ? nO : 0;
             const int nsl = a.nslE + a.nslO;
-            a.nsl_magic = (65536u + (uint32_t)nsl - 1u) / (uint32_t)nsl;
+            a.nsl_magic = pipe_deal_magic(nsl);
             // serving wavefronts per evaluator workgroup (pipe_xserve_request): every launched one can serve
             a.xstride = (T * PP_B + ne_wg - 1) / ne_wg;
-            pb.xserve = a.xserve = xserve_sweep && a.xstride <= PP_WAVES;
+            // nodes per evaluator workgroup: 8 in a launch without resolvers whose items leave half the workgroups
+            // empty - the head (pipe_plan.hpp; DLSM_PIPE_HEAD_SPREAD=0 keeps 16)
+            const int qs = pipe_launch_qshift(T, nbat, parts, ne_wg, l, kn.pipe_head_spread);
+            if (l == -1) h->pipe_head_q = 1 << qs;
+            pb.flags = a.flags = (xserve_sweep && a.xstride <= PP_WAVES ? PP_F_XSERVE : 0) | wt_sweep |
+                                 (qs == 3 ? PP_F_SPREAD : 0);
             launch_pipe_step<DD, DLSM_UNDIRECTED>(h, q, v, pb, dim3(grid), lds, l);
         } else if (h->model == DLSM_UNDIRECTED)
             launch_pipe_step<DD, DLSM_UNDIRECTED>(h, q, v, pb, dim3(grid), lds, l);
@@ -1541,6 +1553,12 @@ int dlsm_resolve_sweep_algo(dlsm_chain *h, int algo) {
     NEED(h, h != nullptr, "null handle");
     int rc = check_sweep_algo(h, algo); if (rc) return rc;
     return resolve_sweep_algo(h, algo);
+}
+
+int dlsm_pipe_head_nodes(dlsm_chain *h, int *nodes) {
+    NEED(h, h && nodes, "null argument");
+    *nodes = h->pipe_head_q;
+    return DLSM_OK;
 }
 
 int dlsm_sweep_positions(dlsm_chain *h, uint32_t iter, int algo) {

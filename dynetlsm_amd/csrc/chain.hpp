@@ -162,6 +162,7 @@ struct dlsm_chain {
     // sweep v2 scratch
     double *spec = nullptr; size_t spec_cap = 0;
     double *pipe = nullptr; size_t pipe_cap = 0;        // pipelined sweep (algo 4) buffers
+    int pipe_head_q = 0;                                // nodes per evaluator workgroup of its last head launch (0: none yet)
     dlsm::SweepCarry carry;
     int n_cu = 256;
     int32_t *nctrl = nullptr; size_t nctrl_cap = 0;     // valid controls per (t, i, dir)

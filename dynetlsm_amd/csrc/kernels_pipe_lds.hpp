@@ -45,6 +45,7 @@ __device__ __forceinline__ unsigned long long scalar_load_u64(const unsigned lon
 #include "pipe_plan.hpp"        // PL_WIN, pipe_lds_trip_cap / _eval_bytes, PipePlan, pipe_plan_entry (plain C++)
 namespace dlsm {
 static_assert(PL_EXPTAB_DOUBLES == EXPTAB11_N, "pipe_plan.hpp sizes the LDS with the evaluators' exp table");
+static_assert(PL_B == PP_B && PL_WAVES == PP_WAVES, "pipe_plan.hpp deals the batch's nodes over the workgroup's wavefronts");
 
 // (pb: the kernel argument itself - the plan entry is a scalar load at a computed offset)
 __device__ __forceinline__ PipePlan pipe_plan(const PipeBuf &pb, int ntrip, int p, int be, int k0) {
@@ -93,7 +94,7 @@ __device__ __forceinline__ void pipe_lds_trips(int nw64, int P, const PipePlan &
                                                int k, int jk, int lane, const double (&xk0)[D],
                                                const double (&xk1)[D], double E, int nflush,
                                                const unsigned long long *yrow, unsigned long long ym,
-                                               const double *etab, const double *sX, const double *sM, double *hrow,
+                                               const double *etab, const double *sX, const double *sM, double *hrow, bool wt,
                                                RatioAcc &ra, Stamps<PIPE_ITEM_T> &st) {
     const int ntp = pl.trips();
     // (nw64: 8-byte words of a row of the network)
@@ -139,7 +140,7 @@ __device__ __forceinline__ void pipe_lds_trips(int nw64, int P, const PipePlan &
 #pragma unroll
                     for (int d = 0; d < D; ++d) xm1[d] = rowm[d];
                     const double h = pipe_h_finish<D, SQ>(xm1, xk0, xk1, d0, d1, e0, e1, f0, f1, yb, E, etab);
-                    hrow[(wq + 2) * 64 + lane] = h;         // [previous batch (128) | own batch (128)]
+                    pipe_store(wt, &hrow[(wq + 2) * 64 + lane], h);     // [previous batch (128) | own batch (128)]
                 }
             }
         }
@@ -224,7 +225,7 @@ __device__ __forceinline__ double wave_prod_tp(double v, int lane) {     // prod
 __device__ __forceinline__ void pipe_xserve_request(const PipeLds &a, int l, int wg, int wave,
                                                     int lane, PipeXServe &xs) {
     xs.on = false;
-    if (!a.xserve || wave >= a.xstride) return;
+    if (!(a.flags & PP_F_XSERVE) || wave >= a.xstride) return;
     const int row = wg * a.xstride + wave;
     if (row >= a.T * PP_B) return;
     const int t = row >> 7, k = row & (PP_B - 1);
@@ -260,11 +261,11 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
     a.X = pb.lds.X; a.ybits = pb.lds.ybits; a.prop = pb.lds.prop; a.full0 = pb.lds.full0; a.H = pb.lds.H;
     a.acc = pb.lds.acc; a.consts = pb.lds.consts; a.xprod = pb.lds.xprod;
     a.T = pb.lds.T; a.N = pb.lds.N; a.W = pb.lds.W; a.squared = pb.lds.squared; a.parts = pb.lds.parts;
-    a.nbat = pb.lds.nbat; a.lds_cap = pb.lds.lds_cap; a.xserve = pb.lds.xserve;
+    a.nbat = pb.lds.nbat; a.lds_cap = pb.lds.lds_cap; a.flags = pb.lds.flags;
     a.beE = pb.lds.beE; a.beO = pb.lds.beO; a.nbE = pb.lds.nbE; a.nbO = pb.lds.nbO; a.nslE = pb.lds.nslE;
     a.nslO = pb.lds.nslO; a.xstride = pb.lds.xstride; a.nsl_magic = pb.lds.nsl_magic;
     asm volatile("" :: "s"(a.X), "s"(a.ybits), "s"(a.prop), "s"(a.full0), "s"(a.H), "s"(a.acc), "s"(a.consts), "s"(a.xprod));
-    asm volatile("" :: "s"(a.T), "s"(a.N), "s"(a.W), "s"(a.squared), "s"(a.parts), "s"(a.nbat), "s"(a.lds_cap), "s"(a.xserve),
+    asm volatile("" :: "s"(a.T), "s"(a.N), "s"(a.W), "s"(a.squared), "s"(a.parts), "s"(a.nbat), "s"(a.lds_cap), "s"(a.flags),
                  "s"(a.beE), "s"(a.beO), "s"(a.nbE), "s"(a.nbO), "s"(a.nslE), "s"(a.nslO), "s"(a.xstride), "s"(a.nsl_magic));
     const int T = a.T, N = a.N;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -274,17 +275,18 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
     double *sTab = lds;
     double *sX = lds + EXPTAB11_N;                                      // [trip cap][64][D]
     double *sM = sX + (size_t)a.lds_cap * 64 * D;                       // [PL_WIN][64][D]
-    // the workgroup's items: 16 consecutive nodes (wg mod 8) of one active slice and part, wg / 8 = p nsl + si;
+    // the workgroup's items: q = 16 or 8 consecutive nodes of one active slice and part (pipe_plan.hpp, pipe_deal);
     // batches, sizes and slice counts of the launch from the host (PipeBuf) - the four wavefronts of a SIMD issue
     // this prologue one after the other, so what it does not compute is time the barrier below comes earlier
     constexpr bool first = true;
     const int wg = (int)blockIdx.x - T;                                  // (also the row server's index)
-    const int wgx = wg & (PP_B / PP_WAVES - 1), wr = wg >> 3;
-    const int p = (int)(((uint32_t)wr * a.nsl_magic) >> 16);
-    const int si = wr - p * (a.nslE + a.nslO);
+    const PipeDeal deal = pipe_deal(wg, (a.flags & PP_F_SPREAD) ? 3 : 4);
+    const int p = pipe_deal_part(deal.r, a.nsl_magic);
+    const int si = deal.r - p * (a.nslE + a.nslO);
+    const bool wt = (a.flags & PP_F_WT) != 0;
     PipeXServe xs;
     {
-        const int k0 = wgx * PP_WAVES;
+        const int k0 = deal.k0;
         const int nslE = a.nslE;
         const bool odd = si >= nslE;
         const int be = odd ? a.beO : a.beE;
@@ -296,7 +298,7 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
         }
         const int t = odd ? 2 * (si - nslE) + 1 : 2 * si;
         const int k = k0 + wave;
-        const bool live = k < nb;
+        const bool live = k < nb && wave < deal.nlive;
         // stamps (profiles/pipe_timing.py): 0 entry, 4 rows + table staged (behind the barrier), 1 first trip done,
         // 2 last trip done, 3 = 5 record stored
         Stamps<PIPE_ITEM_T> st(l + 1, wg * PP_WAVES + wave);
@@ -374,9 +376,9 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
         if (live) {
             RatioAcc ra;
             const bool noflush = nflush >= 64 * ntp && !a.squared;
-            if (noflush) pipe_lds_trips<D, false, false>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, ra, st);
-            else if (a.squared) pipe_lds_trips<D, true, true>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, ra, st);
-            else pipe_lds_trips<D, true, false>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, ra, st);
+            if (noflush) pipe_lds_trips<D, false, false>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, wt, ra, st);
+            else if (a.squared) pipe_lds_trips<D, true, true>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, wt, ra, st);
+            else pipe_lds_trips<D, true, false>(a.W >> 1, P, pl, p, be, k, jk, lane, xk0, xk1, E, nflush, yrow, ym0, sTab, sX, sM, hrow, wt, ra, st);
             double tot_l, tot_r;
             if (noflush) {
                 // the products of the whole wave stay in range: multiply across lanes
@@ -386,7 +388,7 @@ __device__ __forceinline__ void pipe_eval_lds(const ChainView &c, const PipeBuf 
             }
             if (lane == 0) {
                 double2 *f = (double2 *)a.full0 + (uint32_t)((((be & 1) * T + t) * PP_B + k) * P + p);
-                *f = make_double2(tot_l, tot_r);
+                pipe_store2(wt, f, 0u, make_double2(tot_l, tot_r));
             }
             DLSM_STAMP(st, 3, tot_r)
             st.set(5, st.get(3));

@@ -74,14 +74,33 @@ constexpr int PP_ACC_MASK = PP_B + 4;
 struct PipeLds {
     const double *X; const uint32_t *ybits; double *prop; double *full0; double *H; int32_t *acc; double *consts;
     double *xprod;
-    int T, N, W, squared, parts, nbat, lds_cap, xserve;
+    int T, N, W, squared, parts, nbat, lds_cap, flags;      // (flags: PP_F_*, per launch)
     // per launch: the batch evaluated / its nodes / the active slices (even and odd slices); evaluator workgroup e
-    // (blockIdx.x - T) holds 16 consecutive nodes (e mod 8) of active slice si and part p, e / 8 = p nsl + si with
+    // (blockIdx.x - T) holds q = 16 or 8 consecutive nodes (e mod 128 / q) of active slice si and part p,
+    // e / (128 / q) = p nsl + si (pipe_plan.hpp, pipe_deal) with
     // the quotient as a multiplication: r / nsl = r nsl_magic >> 16 (nsl_magic = ceil(2^16 / nsl), r < 2^16 / nsl)
     int beE, beO, nbE, nbO, nslE, nslO, xstride; uint32_t nsl_magic;
     uint32_t plan[4][8];        // the parts' trip lists (pipe_plan_entry), by (window trips - 1, part)
 };
 static_assert(sizeof(PipeLds) == 256, "PipeLds: two 64-byte halves of scalars and the plan table");
+// The launch's switches, one word for both roles (PipeLds::flags for the evaluators, PipeBuf::flags for the resolvers):
+//   PP_F_XSERVE  the evaluators multiply the resolvers' cross products (pipe_xserve_*)
+//   PP_F_WT      what the launch hands to a later one - H rows, item records, accepted positions, the samplers'
+//                bookkeeping, the acceptance masks - is stored write-through (sc1): the readers are on other XCDs
+//                and read from memory either way, and the end-of-kernel release finds nothing dirty to write back
+//                (2 MB per launch as plain stores)
+//   PP_F_SPREAD  8 nodes per evaluator workgroup instead of 16 (pipe_plan.hpp, pipe_launch_qshift)
+constexpr int PP_F_XSERVE = 1, PP_F_WT = 2, PP_F_SPREAD = 4;
+// a hand-off store of the sweep: write-through when the launch says so
+__device__ __forceinline__ void pipe_store(bool wt, double *p, double v) {
+    if (wt) coh_store<true>(p, v); else coh_store<false>(p, v);
+}
+__device__ __forceinline__ void pipe_store2(bool wt, void *base, uint32_t off, double2 v) {
+    if (wt) coh_store2<true>(base, off, v); else coh_store2<false>(base, off, v);
+}
+__device__ __forceinline__ void pipe_store_i32(bool wt, int32_t *p, int32_t v) {
+    if (wt) coh_store_i32(p, v); else *p = v;
+}
 
 // One batch is resolved (and the next one evaluated) per launch.  Batch b is evaluated while batch b - 1 is still
 // unresolved - its WINDOW: the previous batch, if any - and everything produced per batch lives in slot b & 1.
@@ -116,7 +135,7 @@ struct PipeBuf {
     // the cross products by the evaluators (kernels_pipe_lds.hpp, pipe_xserve): slot [t][k] holds PP_XP_EMPTY
     // until the wavefront that serves row k of slice t has stored prod_{m accepted} Hx[k][m]; the row's owner in
     // the resolver workgroup polls it past its L1 and empties it again
-    double *xprod; int32_t *err; int xserve, budget;
+    double *xprod; int32_t *err; int flags, budget;     // (flags: PP_F_*, per launch)
     int lds_eval;    // undirected model: the evaluators of kernels_pipe_lds.hpp (rows staged in LDS, interleaved
                      // parts, H factors inside the trips); 0: pipe_eval_item
 };
@@ -514,19 +533,27 @@ __device__ __forceinline__ void row_resolve(const ChainView &c, const PipeBuf &p
         const unsigned long long m0 = sMask[cur][0], m1 = sMask[cur][1];
         const unsigned long long mine = half == 0 ? m0 : m1;
         const int accepted = (int)((mine >> lane) & 1ull);
+        // (all of it for later launches: write-through under PP_F_WT, like the evaluators' rows and records)
+        const bool wt = (pb.flags & PP_F_WT) != 0;
         if (valid) {
             const size_t tj = (size_t)t * N + j0 + k;
             if (accepted) {
 #pragma unroll
-                for (int d = 0; d < D; ++d) coh_store<false>(&c.X[tj * D + d], x1[d]);
+                for (int d = 0; d < D; ++d) pipe_store(wt, &c.X[tj * D + d], x1[d]);
             }
             metropolis_bookkeeping(st, na, ns, un, c.tune, c.tune_interval, accepted);
-            c.step[tj] = st; c.nacc[tj] = na; c.nsteps[tj] = ns; c.until[tj] = un;
+            pipe_store(wt, &c.step[tj], st);
+            pipe_store_i32(wt, &c.nacc[tj], na); pipe_store_i32(wt, &c.nsteps[tj], ns); pipe_store_i32(wt, &c.until[tj], un);
         }
         // the next batch's window: this batch's acceptances, as a mask
         if (tid == 0) {
             unsigned long long *pmw = (unsigned long long *)(pb.acc + ((size_t)t * 2 + (b & 1)) * PP_ACC + PP_ACC_MASK);
-            pmw[0] = m0; pmw[1] = m1;
+            if (wt) {
+                __hip_atomic_store(pmw, m0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(pmw + 1, m1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else {
+                pmw[0] = m0; pmw[1] = m1;
+            }
         }
     }
     DLSM_STAMP(rst, 4, (double)cur)
@@ -577,7 +604,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pipe_step(ChainView c, PipeBuf p
         __shared__ double sCross[PP_B];
         __shared__ unsigned long long sSatMask[2];
         __shared__ double sTab[EXPTAB_N];
-        const bool served = pb.xserve != 0 && grid3;                  // (both sides decide by the same rule)
+        const bool served = (pb.flags & PP_F_XSERVE) != 0 && grid3;                 // (both sides decide by the same rule)
         if (l == -1 && threadIdx.x < PP_B)                            // the sweep's first launch: every slot empty
             pb.xprod[(size_t)t * PP_B + threadIdx.x] = __longlong_as_double((long long)PP_XP_EMPTY);
         if (b < 0 || b >= pb.nbat) return;

@@ -66,4 +66,55 @@ DLSM_PLAN_HD inline PipePlan pipe_plan_from_entry(uint32_t e, int ntrip, int be,
     return pl;
 }
 
+// ---- the deal: which (active slice, part, node) a wavefront of an evaluator workgroup takes -----------------------
+// Evaluator workgroup e of a launch holds q = 2^qs consecutive nodes of one active slice and part, one per wavefront
+// (its first q wavefronts; all sixteen stage the part's rows): e = (p nsl + si) (PL_B / q) + node group.  q = 16
+// fills the workgroup; q = 8 spreads a launch that has few items over twice the workgroups, so that a SIMD issues
+// two items instead of four.
+constexpr int PL_B = 128;           // = PP_B: nodes per batch, node slots per (slice, part)
+constexpr int PL_WAVES = 16;        // = PP_WAVES: wavefronts per evaluator workgroup
+
+// the evaluator workgroups of a launch on n_cu compute units beside its T resolvers, and the parts of a node: as
+// many as fill those workgroups' wavefronts (at most 8: PipeLds::plan) - for the undirected model in ONE round of
+// items, a part less when rounding up would leave items for a second round
+inline int pipe_eval_workgroups(int n_cu, int T) { return n_cu / 2 > n_cu - T ? n_cu / 2 : n_cu - T; }
+inline int pipe_parts(int ne_wg, int T, bool one_round) {
+    int parts = (int)((double)ne_wg * PL_WAVES / ((double)T * PL_B) + 0.5);
+    parts = parts < 1 ? 1 : parts > 8 ? 8 : parts;
+    if (one_round && parts > 1 && (long)parts * T * PL_B > (long)ne_wg * PL_WAVES) --parts;
+    return parts;
+}
+inline int pipe_parts_undirected(int ne_wg, int T) { return pipe_parts(ne_wg, T, true); }
+
+// launch l resolves batch l of the even slices and batch l - 1 of the odd ones (kernels_spec_pipe.hpp)
+DLSM_PLAN_HD inline bool pipe_launch_resolves(int T, int nbat, int l) {
+    return (l >= 0 && l < nbat) || (T > 1 && l >= 1 && l - 1 < nbat);
+}
+// ... and evaluates batch l + 1 of the even slices and batch l of the odd ones: its active slices
+DLSM_PLAN_HD inline int pipe_launch_slices(int T, int nbat, int l) {
+    const int nE = (T + 1) / 2, nO = T / 2;
+    return (l + 1 >= 0 && l + 1 < nbat ? nE : 0) + (l >= 0 && l < nbat ? nO : 0);
+}
+// log2 of the nodes per evaluator workgroup of launch l: 3 (q = 8) when the launch's items, eight to a workgroup,
+// still fit its ne_wg evaluator workgroups and no resolver of the launch has a batch to resolve - a launch that
+// carries resolvers is as long as they are, and halving its evaluators' trips buys nothing; 4 (q = 16) otherwise
+DLSM_PLAN_HD inline int pipe_launch_qshift(int T, int nbat, int parts, int ne_wg, int l, bool spread) {
+    if (!spread || pipe_launch_resolves(T, nbat, l)) return 4;
+    const long wgs8 = (long)parts * pipe_launch_slices(T, nbat, l) * (PL_B / 8);
+    return wgs8 > 0 && wgs8 <= (long)ne_wg ? 3 : 4;
+}
+// evaluator workgroup e: its node group's first node k0, its live wavefronts, and r = p nsl + si
+struct PipeDeal { int k0, nlive, r; };
+DLSM_PLAN_HD inline PipeDeal pipe_deal(int e, int qs) {
+    PipeDeal d;
+    d.k0 = (e & ((PL_B >> qs) - 1)) << qs;
+    d.nlive = 1 << qs;
+    d.r = e >> (7 - qs);
+    return d;
+}
+static_assert(PL_B == 1 << 7, "pipe_deal: node groups by shifts");
+// r / nsl as a multiplication (r < 2^16 / nsl): the magic number the host computes, and the quotient
+inline uint32_t pipe_deal_magic(int nsl) { return (65536u + (uint32_t)nsl - 1u) / (uint32_t)nsl; }
+DLSM_PLAN_HD inline int pipe_deal_part(int r, uint32_t nsl_magic) { return (int)(((uint32_t)r * nsl_magic) >> 16); }
+
 }  // namespace dlsm

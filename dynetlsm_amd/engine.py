@@ -377,6 +377,13 @@ class Chain(object):
             self._ck(rc)
         return rc
 
+    def pipe_head_nodes(self):
+        """nodes per evaluator workgroup of the last pipelined sweep's head launch: 16, or 8 when it was
+        spread over twice the workgroups; 0 before the first such sweep"""
+        q = C.c_int(0)
+        self._ck(self._L.dlsm_pipe_head_nodes(self._h, C.byref(q)))
+        return int(q.value)
+
     def center(self):
         self._ck(self._L.dlsm_center(self._h))
 

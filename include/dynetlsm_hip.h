@@ -144,6 +144,9 @@ int dlsm_sweep_positions(dlsm_chain *h, uint32_t iter, int algo);
 /* the algorithm `algo` resolves to for this handle (what 0 = auto picks): 1, 2, 4 or 5; a
  * non-zero `algo` is returned as it is after the same checks as dlsm_sweep_positions */
 int dlsm_resolve_sweep_algo(dlsm_chain *h, int algo);
+/* nodes per evaluator workgroup of the last pipelined sweep's (algo 4) head launch: 16, or 8 when the
+ * launch was spread over twice the workgroups (DLSM_PIPE_HEAD_SPREAD); 0 before the first such sweep */
+int dlsm_pipe_head_nodes(dlsm_chain *h, int *nodes);
 /* lsm.py:501 / hdp_lpcm.py:852 */
 int dlsm_center(dlsm_chain *h);
 /* longitudinal_procrustes_rotation (procrustes.py:28-35): X <- X R with
