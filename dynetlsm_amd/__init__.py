@@ -19,6 +19,8 @@ from .loo import loo, compare_loo, LooResult  # noqa
 from .scores import in_sample_scores, ScoreResult  # noqa
 from .convergence import convergence_diagnostics, ConvergenceResult  # noqa
 from .probabilities import edge_probabilities, EdgeProbabilityResult  # noqa
+from . import dynamics  # noqa
+from .dynamics import tie_dynamics, TieDynamicsResult  # noqa
 from . import forecast  # noqa  (the one-step module; calling it is forecast_paths.forecast)
 from .forecast_paths import ForecastResult  # noqa
 
@@ -28,4 +30,5 @@ __all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
            'DirectedCaseControlSampler', 'posterior_predictive_check', 'GofResult',
            'information_criteria', 'compare_information_criteria', 'ICResult', 'loo', 'compare_loo', 'LooResult',
            'in_sample_scores', 'ScoreResult', 'convergence_diagnostics', 'ConvergenceResult', 'forecast',
-           'ForecastResult', 'edge_probabilities', 'EdgeProbabilityResult']
+           'ForecastResult', 'edge_probabilities', 'EdgeProbabilityResult', 'dynamics', 'tie_dynamics',
+           'TieDynamicsResult']

@@ -38,6 +38,7 @@
 #include "kernels_conv.hpp"
 #include "kernels_loo.hpp"
 #include "kernels_proba.hpp"
+#include "kernels_dynamics.hpp"
 #include "kernels_missing.hpp"
 #include "host_draws.hpp"
 
@@ -2230,6 +2231,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_conv.hpp"
 #include "capi_loo.hpp"
 #include "capi_proba.hpp"
+#include "capi_dynamics.hpp"
 #include "capi_forecast_paths.hpp"
 #include "capi_hdp.hpp"
 

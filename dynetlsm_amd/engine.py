@@ -1000,6 +1000,48 @@ class Chain(object):
             hist_width.ctypes.data_as(u64), _p(pw) if pointwise else None))
         return calib, brier, node_sums, hist_width, pw
 
+    # -- tie dynamics (no reference counterpart) ---------------------------------------------------
+    def dynamics_accumulate(self, bits, Xs, intercepts, radii, min_count, mask=None, n_bins=20, pointwise=False):
+        """The posterior change of the edge probability of every dyad between consecutive time steps over the
+        S >= 2 samples (arguments as ``proba_accumulate``; the chain has T >= 2), in one pass on the device
+        (csrc/kernels_dynamics.hpp; the definition: include/dynetlsm_hip.h).  A step u = t -> t + 1 of a dyad is
+        scored when ``mask`` excludes it neither at t nor at t + 1.  Returns uint64 tables over the scored steps -
+        ``transitions`` (T - 1, 4, 4): per observed class 2 y_t + y_{t+1} the dyads and the sums of the mean
+        probability at t, at t + 1 and of the mean of their product, in units of 2^-32; ``hist_up`` (T - 1,
+        n_bins): dyads per bin min(up * n_bins // S, n_bins - 1) of the number of samples in which the linear
+        predictor rose; ``node_changes`` (T - 1, N, 4): dyad (i, j) that rose in at least ``min_count`` (1..S)
+        samples adds 1 to slot 0 of i and slot 1 of j, one that fell in as many to slots 2 and 3;
+        ``node_turnover`` (T - 1, N, 2): |mean change| in units of 2^-32 to slot 0 of i and slot 1 of j - and, with
+        ``pointwise``, (T - 1, N, N, 4) = (delta_mean, delta_sd, prob_up, prob_down) of every dyad (undirected:
+        i < j filled, the rest 0), else None."""
+        if self.T < 2:
+            raise ValueError('a step needs two time steps, the chain has T=%d' % self.T)
+        n_bins = int(n_bins)
+        if not 1 <= n_bins <= 64:
+            raise ValueError('n_bins must be between 1 and 64, got %d' % n_bins)
+        bits = self._packed(bits, 'bits')
+        if mask is not None:
+            mask = self._packed(mask, 'mask')
+        if np.shape(Xs)[0] < 2:
+            raise ValueError('needs at least two samples (the standard deviation has ddof = 1)')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii)
+        if int(min_count) != min_count or not 1 <= int(min_count) <= S:
+            raise ValueError('min_count must be an integer between 1 and S=%d, got %r' % (S, min_count))
+        U = self.T - 1
+        transitions = np.zeros((U, 4, 4), dtype=np.uint64)
+        hist_up = np.zeros((U, n_bins), dtype=np.uint64)
+        node_changes = np.zeros((U, self.N, 4), dtype=np.uint64)
+        node_turnover = np.zeros((U, self.N, 2), dtype=np.uint64)
+        pw = np.zeros((U, self.N, self.N, 4)) if pointwise else None
+        u64 = _lib.c_u64_p
+        self._ck(self._L.dlsm_dynamics_accumulate(
+            self._h, bits.ctypes.data_as(_lib.c_u32_p),
+            mask.ctypes.data_as(_lib.c_u32_p) if mask is not None else None, _p(Xs), _p(b),
+            _p(r) if r is not None else None, int(S), int(min_count), n_bins, transitions.ctypes.data_as(u64),
+            hist_up.ctypes.data_as(u64), node_changes.ctypes.data_as(u64), node_turnover.ctypes.data_as(u64),
+            _p(pw) if pointwise else None))
+        return transitions, hist_up, node_changes, node_turnover, pw
+
     # -- multi-step posterior predictive forecasts (the reference: one step, undirected, on the host) ----
     def forecast_paths(self, X0, intercepts, radii=None, z0=None, trans=None, mu=None, sigma=None, lmbda=None,
                        sigma_sq=0.0, horizon=1, seed=0, first_index=0, batch=0, want_paths=False,

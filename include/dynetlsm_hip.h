@@ -550,6 +550,39 @@ int dlsm_proba_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *m
                           const double *width_edges, int n_edges, uint64_t *calib, uint64_t *brier,
                           uint64_t *node_sums, uint64_t *hist_width, double *pointwise);
 
+/* ---- tie dynamics (posterior change of the edge probabilities between steps) ---- */
+/* No reference counterpart.  A step u = t -> t + 1 (u = 0 .. T - 2) of a dyad of the handle (undirected: i < j;
+ * directed and case-control: i != j; the same linear predictor eta, the same samples Xs S*T*N*D, intercepts S*2,
+ * radii S*N or NULL as dlsm_proba_accumulate takes them), with p_{s,t} = expit(eta_{s,t}), over the S samples in one
+ * pass - the joint posterior of two consecutive time steps:
+ *   delta_mean, delta_sd (ddof 1) of d_s = p_{s,t+1} - p_{s,t}
+ *   up = the samples with eta_{s,t+1} > eta_{s,t}, down = those with < (a tie counts as neither);
+ *   prob_up = up / S, prob_down = down / S
+ *   persist = mean_s p_{s,t} p_{s,t+1}, and the marginals pbar_t, pbar_{t+1}
+ * Both etas of a step come from the same instructions: they are equal exactly when the two time steps' inputs are.
+ * A step of a dyad is scored when its bit in `mask` (NULL, or T*N*W uint32 packed like the network `bits`; undirected
+ * handles: either of (i, j), (j, i)) is set neither at t nor at t + 1.  With fix(x) = llrint(x 2^32), over the scored
+ * steps u:
+ *   transitions    (T-1)*4*4 uint64: per observed class c = 2 y_t + y_{t+1} the dyads, sum fix(pbar_t),
+ *                  sum fix(pbar_{t+1}) and sum fix(persist)
+ *   hist_up        (T-1)*n_bins uint64: dyads per bin b = min(up * n_bins / S, n_bins - 1), in integer arithmetic
+ *   node_changes   (T-1)*N*4 uint64: dyad (i, j) with up >= min_count adds 1 to slot 0 of node i and to slot 1 of
+ *                  node j, with down >= min_count to slot 2 of i and slot 3 of j
+ *   node_turnover  (T-1)*N*2 uint64: fix(|delta_mean|) is added to slot 0 of node i and to slot 1 of node j (the
+ *                  convention of node_sums of dlsm_proba_accumulate)
+ *   pointwise      NULL or (T-1)*N*N*4: (delta_mean, delta_sd, prob_up, prob_down) of every dyad (u, i, j), scored or
+ *                  not; undirected: i < j filled, the rest 0
+ * Everything accumulated across dyads is an integer added with 64-bit atomics: the same call returns the same bits,
+ * whatever the order, with and without `pointwise`.  The fixed point costs at most half a unit of 2^-32 per dyad.
+ * S < 2, a handle with T < 2, min_count outside 1..S, n_bins outside 1..64, radii NULL on a directed handle ->
+ * DLSM_E_ARG; a set diagonal or padding bit of `bits`, a radius <= 0 -> DLSM_E_DATA.  2^31 or more dyads per time
+ * step (the sums stay below 2^63), or samples that do not fit the device -> DLSM_E_LIMIT; for the samples the message
+ * names the largest S that fits. */
+int dlsm_dynamics_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *mask, const double *Xs,
+                             const double *intercepts, const double *radii, int S, int min_count, int n_bins,
+                             uint64_t *transitions, uint64_t *hist_up, uint64_t *node_changes,
+                             uint64_t *node_turnover, double *pointwise);
+
 /* ---- multi-step posterior predictive forecasts --------------------------- */
 /* The reference has only the one-step undirected form (hdp_lpcm.py:555-626, drawn on the host).  One
  * trajectory of H future time steps per sample s, started at the sample's last time step X0 S*N*D:
