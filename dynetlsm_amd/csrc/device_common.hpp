@@ -163,6 +163,27 @@ __device__ __forceinline__ void coh_load_row(const void *base, uint32_t off, dou
 }
 __device__ __forceinline__ void drain_vmem() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// ---- wave-uniform words through the scalar cache --------------------------------
+// Loads from the constant address space at a wave-uniform address: scalar loads straight into the SGPRs a
+// lane mask or a scalar popcount reads.  For data no kernel writes while another reads it this way (the packed
+// network: whoever rewrites it - the missing dyads' sampler - does so in a launch of its own, and the kernel
+// boundary invalidates the scalar cache).
+#define DLSM_CONSTANT_AS __attribute__((address_space(4)))
+typedef unsigned long long dlsm_u64x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ unsigned long long scalar_load_u64(const unsigned long long *p) {
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    return *(const DLSM_CONSTANT_AS unsigned long long *)p;
+#pragma clang diagnostic pop
+}
+// four consecutive words at a 32-byte aligned address: one s_load_dwordx8
+__device__ __forceinline__ dlsm_u64x4 scalar_load_u64x4(const unsigned long long *p) {
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    return *(const DLSM_CONSTANT_AS dlsm_u64x4 *)p;
+#pragma clang diagnostic pop
+}
+
 // ---- reductions ------------------------------------------------------------
 // All-lanes reductions of a 64-wide wavefront without LDS traffic: four DPP steps inside
 // each row of 16 lanes (quad_perm xor 1, xor 2, row_half_mirror, row_mirror: after them
@@ -335,11 +356,32 @@ constexpr int EXPTAB_N = 256;
 __device__ __forceinline__ void exp_table_fill(double *tab, int tid) {
     if (tid < EXPTAB_N) tab[tid] = c_exp2_tab[tid];
 }
-__device__ __forceinline__ double tab_exp(double x, const double *tab) {
+// PIN (the undirected log-likelihood pass, four exponentials per trip): the exponent word ki >> 8 is computed
+// where the reduced argument r is - the empty asm takes both as operands, so the shift stands in front of the
+// polynomial instead of in front of the ldexp - and the polynomial's literal 1 / 6 comes in a register of the
+// caller's, pinned once outside its loop (exp_sixth_pinned): left to itself the compiler re-materialised it every
+// trip, because it reused the literal's register as an accumulator.  The asm is not volatile: the exponentials
+// of a trip still interleave.  Same fmas, same table entry, same ldexp: the same value bit for bit.  Measured
+// in the pass only (profiles/hot_loop_diet.md); every other caller keeps the plain form.
+// DLSM_EXP_UNPINNED: neither of the two, for A / B builds.
+#ifdef DLSM_EXP_UNPINNED
+__device__ __forceinline__ void exp_pin_low(double &, int &) {}
+__device__ __forceinline__ double exp_sixth_pinned() { return 1.0 / 6.0; }
+#else
+__device__ __forceinline__ void exp_pin_low(double &r, int &ke) { asm("" : "+v"(r), "+v"(ke)); }
+__device__ __forceinline__ double exp_sixth_pinned() {
+    double s = 1.0 / 6.0;
+    asm volatile("" : "+v"(s));
+    return s;
+}
+#endif
+template <bool PIN = false>
+__device__ __forceinline__ double tab_exp(double x, const double *tab, double sixth = 1.0 / 6.0) {
     const double magic = 6755399441055744.0;                     // 1.5 * 2^52
     const double t = fma(x, 369.3299304675746, magic);           // 256 / ln2
-    const double kf = t - magic;
     const int ki = __double2loint(t);
+    int ke = ki >> 8;
+    const double kf = t - magic;
 #ifdef DLSM_EXP_TWO_STEP
     double r = fma(kf, -0x1.62e42fee00000p-9, x);                // ln2 / 256, high 32 bits
     r = fma(kf, -0x1.a39ef35793c76p-41, r);
@@ -347,18 +389,20 @@ __device__ __forceinline__ double tab_exp(double x, const double *tab) {
     // one step with ln2 / 256 rounded to double: the product is exact inside the fma, so the only
     // error is the constant's rounding, |x| 1.1e-16 on the reduced argument = on e^x relatively
     // (1e-15 at a distance of 10, 9e-15 at 80, where e^x is 1e-35) - one instruction of twelve
-    const double r = fma(kf, -0x1.62e42fefa39efp-9, x);
+    double r = fma(kf, -0x1.62e42fefa39efp-9, x);
 #endif
-    double p = fma(r, 1.0 / 24.0, 1.0 / 6.0);
+    if (PIN) exp_pin_low(r, ke);
+    double p = fma(r, 1.0 / 24.0, sixth);
     p = fma(p, r, 0.5);
     p = fma(p, r, 1.0);
     p = fma(p, r, 1.0);
-    return __builtin_ldexp(tab[ki & (EXPTAB_N - 1)] * p, ki >> 8);
+    return __builtin_ldexp(tab[ki & (EXPTAB_N - 1)] * p, ke);
 }
 
 // any x <= 0: e^x is 0 in double below -745.2
-__device__ __forceinline__ double tab_exp_clamped(double x, const double *tab) {
-    return tab_exp(fmax(x, -1000.0), tab);
+template <bool PIN = false>
+__device__ __forceinline__ double tab_exp_clamped(double x, const double *tab, double sixth = 1.0 / 6.0) {
+    return tab_exp<PIN>(fmax(x, -1000.0), tab, sixth);
 }
 
 // The same scheme on a 2048-entry table of 2^(j / 2048) (16 KB of LDS): |r| <= ln2 / 4096 = 1.7e-4,

@@ -221,19 +221,43 @@ __global__ __launch_bounds__(LLU_THREADS) __attribute__((amdgpu_waves_per_eu(D <
             else if ((R_) == 3 * LLU_ROWS / 4) __builtin_amdgcn_s_setprio(0);                  \
         }
 #endif
+    // The four row words of a trip: 32 contiguous, 32-byte aligned bytes (i0 a multiple of 64, r of 4, Ncm of
+    // 128) at a wave-uniform address - ONE scalar load (s_load_dwordx8) straight into the registers the lane
+    // masks and the popcounts read.  (As plain loads through c.ycm they were two vector loads and eight
+    // v_readfirstlane per trip.)  Scalar loads share a counter with the LDS reads and return out of order, so an
+    // outstanding one makes every wait for an LDS read a wait for everything: trip r + 1's words are therefore
+    // requested at the top of trip r, in front of its row reads, and are long there when that trip's table
+    // reads are waited for.  The last trip requests its own words again (nothing beyond the tile is read).
+    // c.ycm changes only between launches (the missing dyads' sampler rewrites it in a launch of its own; no kernel
+    // reads it through the scalar cache while another writes it, and the kernel boundary invalidates that cache).
+    // DLSM_LLU_VECTOR_WORDS: the plain loads this replaced, for A / B builds.
+    static_assert(U == 4 && LLU_ROWS % U == 0, "four row words per scalar load");
+#ifdef DLSM_LLU_VECTOR_WORDS
+#define DLSM_LLU_WORDS_DECL(NEXT_, FIRST_)
+#define DLSM_LLU_WORDS_TAKE(YM_, NEXT_, AHEAD_, HERE_, REV_)                                   \
+        _Pragma("unroll")                                                                      \
+        for (int u = 0; u < U; ++u) YM_[u] = (HERE_)[(REV_) ? U - 1 - u : u];
+#else
+#define DLSM_LLU_WORDS_DECL(NEXT_, FIRST_) dlsm_u64x4 NEXT_ = scalar_load_u64x4(FIRST_);
+#define DLSM_LLU_WORDS_TAKE(YM_, NEXT_, AHEAD_, HERE_, REV_)                                   \
+        _Pragma("unroll")                                                                      \
+        for (int u = 0; u < U; ++u) YM_[u] = NEXT_[(REV_) ? U - 1 - u : u];                    \
+        NEXT_ = scalar_load_u64x4(AHEAD_);
+#endif
+    // (the exponential's literal 1 / 6 in a register of its own: device_common.hpp)
+    const double sixth = exp_sixth_pinned();
 #define DLSM_LLU_TRIPS(WHOLE_, SQ_)                                                            \
+    DLSM_LLU_WORDS_DECL(ynext, ywords)                                                         \
     for (int r = 0; r < LLU_ROWS; r += U) {                                                    \
         DLSM_LLU_PRIO(r)                                                                       \
         unsigned long long ym[U];                                                              \
-        _Pragma("unroll")                                                                      \
-        for (int u = 0; u < U; ++u)                                                            \
-            ym[u] = ywords[r + u];                                                             \
+        DLSM_LLU_WORDS_TAKE(ym, ynext, ywords + min(r + U, LLU_ROWS - U), ywords + r, false)   \
         double dd[U], e[U];                                                                    \
         _Pragma("unroll")                                                                      \
         for (int u = 0; u < U; ++u) dd[u] = dist_fast<D>(&sXi[(r + u) * D], xj, SQ_);          \
         _Pragma("unroll")                                                                      \
         for (int u = 0; u < U; ++u)                                                            \
-            e[u] = (SQ_) ? tab_exp_clamped(-dd[u], sTab) : tab_exp(-dd[u], sTab);              \
+            e[u] = (SQ_) ? tab_exp_clamped<true>(-dd[u], sTab, sixth) : tab_exp<true>(-dd[u], sTab, sixth); \
         _Pragma("unroll")                                                                      \
         for (int u = 0; u < U; ++u) {                                                          \
             const bool ok = WHOLE_ || r + u < rend;                                            \
@@ -267,11 +291,14 @@ __global__ __launch_bounds__(LLU_THREADS) __attribute__((amdgpu_waves_per_eu(D <
         for (int d = 0; d < D; ++d) xjb[d] = jb_ < N ? Xt[(size_t)jb_ * D + d] : 0.0;          \
         const unsigned long long va_ = __ballot(j < N), vb_ = __ballot(jb_ < N);               \
         const unsigned long long *ywb = ywords + c.Ncm + LLU_ROWS;                             \
+        /* (the second triangle's rows descend: yb[u] = ywb[63 - r - u], the aligned four at 60 - r reversed) */ \
+        DLSM_LLU_WORDS_DECL(yanext, ywords)                                                    \
+        DLSM_LLU_WORDS_DECL(ybnext, ywb + (LLU_ROWS - U))                                      \
         for (int r = 0; r < LLU_ROWS; r += U) {                                                \
             DLSM_LLU_PRIO(r)                                                                   \
             unsigned long long ya[U], yb[U];                                                   \
-            _Pragma("unroll")                                                                  \
-            for (int u = 0; u < U; ++u) { ya[u] = ywords[r + u]; yb[u] = ywb[LLU_ROWS - 1 - (r + u)]; } \
+            DLSM_LLU_WORDS_TAKE(ya, yanext, ywords + min(r + U, LLU_ROWS - U), ywords + r, false) \
+            DLSM_LLU_WORDS_TAKE(yb, ybnext, ywb + max(LLU_ROWS - 2 * U - r, 0), ywb + (LLU_ROWS - U - r), true) \
             double dd[U], e[U];                                                                \
             unsigned long long okm[U];                                                         \
             _Pragma("unroll")                                                                  \
@@ -290,7 +317,7 @@ __global__ __launch_bounds__(LLU_THREADS) __attribute__((amdgpu_waves_per_eu(D <
             }                                                                                  \
             _Pragma("unroll")                                                                  \
             for (int u = 0; u < U; ++u)                                                        \
-                e[u] = (SQ_) ? tab_exp_clamped(-dd[u], sTab) : tab_exp(-dd[u], sTab);          \
+                e[u] = (SQ_) ? tab_exp_clamped<true>(-dd[u], sTab, sixth) : tab_exp<true>(-dd[u], sTab, sixth); \
             _Pragma("unroll")                                                                  \
             for (int u = 0; u < U; ++u) {                                                      \
                 const unsigned long long live = ya[u] & okm[u];                                \
@@ -319,6 +346,8 @@ __global__ __launch_bounds__(LLU_THREADS) __attribute__((amdgpu_waves_per_eu(D <
     else { DLSM_LLU_TRIPS(false, 0) }
 #undef DLSM_LLU_TRIPS
 #undef DLSM_LLU_TRIPS_DIAG
+#undef DLSM_LLU_WORDS_TAKE
+#undef DLSM_LLU_WORDS_DECL
 #undef DLSM_LLU_PRIO
     // nflush == 64: all chains together hold <= 64 factors (1 + E) <= e^(600 / 64) each
     if (nflush >= LLU_ROWS) {

@@ -31,15 +31,7 @@
 
 namespace dlsm {
 
-#define DLSM_CONSTANT_AS __attribute__((address_space(4)))
-
-// wave-uniform 8-byte word through the scalar cache (read-only data: the packed network)
-__device__ __forceinline__ unsigned long long scalar_load_u64(const unsigned long long *p) {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    return *(const DLSM_CONSTANT_AS unsigned long long *)p;
-#pragma clang diagnostic pop
-}
+// (scalar_load_u64 - a wave-uniform 8-byte word through the scalar cache - is device_common.hpp's)
 
 }  // namespace dlsm
 #include "pipe_plan.hpp"        // PL_WIN, pipe_lds_trip_cap / _eval_bytes, PipePlan, pipe_plan_entry (plain C++)
