@@ -202,6 +202,13 @@ struct ProfScope {
     }
 };
 
+// a device allocation of one C-ABI call, freed when the call returns
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) hipFree(p); }
+    template <typename T> T *as() const { return (T *)p; }
+};
+
 template <typename T>
 int dev_alloc(dlsm_chain *h, T **p, size_t n) {
     HIPCHK(h, hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));

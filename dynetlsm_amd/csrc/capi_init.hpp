@@ -7,12 +7,6 @@ namespace {
 
 using dlsm_host::tridiag_top;
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    template <typename T> T *as() const { return (T *)p; }
-};
-
 int init_need_hops(dlsm_chain *h) {
     NEED(h, h->have_hops, "hop matrices not computed (dlsm_init_shortest_paths)");
     return DLSM_OK;

@@ -1,5 +1,5 @@
-// C-ABI of the post-loop processing (included by capi.hip after capi_init.hpp, which
-// provides DevBuf; the FAIL / HIPCHK / NEED macros come from capi.hip).
+// C-ABI of the post-loop processing (included by capi.hip, which provides DevBuf and
+// the FAIL / HIPCHK / NEED macros).
 #pragma once
 
 extern "C" {

@@ -96,7 +96,16 @@ def _p(a):
         return a.ctypes.data_as(c_i64_p)
     if a.dtype == np.int32:
         return a.ctypes.data_as(c_i32_p)
+    if a.dtype == np.uint32:
+        return a.ctypes.data_as(_lib.c_u32_p)
+    if a.dtype == np.uint64:
+        return a.ctypes.data_as(_lib.c_u64_p)
     raise TypeError(a.dtype)
+
+
+def _po(a):
+    """``_p`` of an optional array: NULL for None and for an empty one"""
+    return _p(a) if a is not None and a.size else None
 
 
 class SamplerGrid(object):
@@ -863,9 +872,8 @@ class Chain(object):
         totals = np.zeros((self.T, 5))
         sample_loglik = np.zeros((S, self.T))
         pw = np.zeros((self.T, self.N, self.N, 2)) if want_pointwise else None
-        self._ck(self._L.dlsm_ic_accumulate(
-            self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(Xs), _p(b), _p(r) if r is not None else None,
-            int(S), _p(totals), _p(sample_loglik), _p(pw) if want_pointwise else None))
+        self._ck(self._L.dlsm_ic_accumulate(self._h, _p(bits), _p(Xs), _p(b), _po(r), int(S), _p(totals),
+                                            _p(sample_loglik), _po(pw)))
         return (totals, sample_loglik, pw) if want_pointwise else (totals, sample_loglik)
 
     # -- in-sample scores (no reference counterpart) --------------------------------------------
@@ -882,10 +890,8 @@ class Chain(object):
         Xs, b, r, S = self._sample_args(Xs, intercepts, radii)
         counts = np.zeros((self.T + 1, 4), dtype=np.uint64)
         logloss_sum = np.zeros(self.T)
-        self._ck(self._L.dlsm_score_accumulate(
-            self._h, bits.ctypes.data_as(_lib.c_u32_p),
-            mask.ctypes.data_as(_lib.c_u32_p) if mask is not None else None, _p(Xs), _p(b),
-            _p(r) if r is not None else None, int(S), counts.ctypes.data_as(_lib.c_u64_p), _p(logloss_sum)))
+        self._ck(self._L.dlsm_score_accumulate(self._h, _p(bits), _po(mask), _p(Xs), _p(b), _po(r), int(S),
+                                               _p(counts), _p(logloss_sum)))
         return counts, logloss_sum
 
     # -- convergence of every dyad (no reference counterpart) -----------------------------------
@@ -924,10 +930,8 @@ class Chain(object):
         node_ess = np.zeros((self.T, self.N))
         pw = np.zeros((self.T, self.N, self.N, 2)) if want_pointwise else None
         self._ck(self._L.dlsm_convergence_accumulate(
-            self._h, _p(Xs), _p(b), _p(r) if r is not None else None, n_segments, seg_len, batch_len,
-            _p(re_) if re_.size else None, int(re_.size), _p(ee) if ee.size else None, int(ee.size),
-            hist_rhat.ctypes.data_as(_lib.c_u64_p), hist_ess.ctypes.data_as(_lib.c_u64_p), _p(node_rhat),
-            _p(node_ess), _p(pw) if want_pointwise else None))
+            self._h, _p(Xs), _p(b), _po(r), n_segments, seg_len, batch_len, _po(re_), int(re_.size), _po(ee),
+            int(ee.size), _p(hist_rhat), _p(hist_ess), _p(node_rhat), _p(node_ess), _po(pw)))
         out = (hist_rhat, hist_ess, node_rhat, node_ess)
         return out + (pw,) if want_pointwise else out
 
@@ -950,10 +954,8 @@ class Chain(object):
         hist_k = np.zeros((self.T, ke.size + 1), dtype=np.uint64)
         node_k = np.zeros((self.T, self.N))
         pw = np.zeros((self.T, self.N, self.N, 2)) if want_pointwise else None
-        self._ck(self._L.dlsm_loo_accumulate(
-            self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(Xs), _p(b), _p(r) if r is not None else None,
-            int(S), _p(ke) if ke.size else None, int(ke.size), _p(totals),
-            hist_k.ctypes.data_as(_lib.c_u64_p), _p(node_k), _p(pw) if want_pointwise else None))
+        self._ck(self._L.dlsm_loo_accumulate(self._h, _p(bits), _p(Xs), _p(b), _po(r), int(S), _po(ke), int(ke.size),
+                                             _p(totals), _p(hist_k), _p(node_k), _po(pw)))
         return (totals, hist_k, node_k, pw) if want_pointwise else (totals, hist_k, node_k)
 
     # -- posterior edge probabilities (no reference counterpart) ----------------------------------
@@ -991,13 +993,9 @@ class Chain(object):
         node_sums = np.zeros((self.T, self.N, 2), dtype=np.uint64)
         hist_width = np.zeros((self.T, we.size + 1), dtype=np.uint64)
         pw = np.zeros((self.T, self.N, self.N, 4)) if pointwise else None
-        u64 = _lib.c_u64_p
         self._ck(self._L.dlsm_proba_accumulate(
-            self._h, bits.ctypes.data_as(_lib.c_u32_p),
-            mask.ctypes.data_as(_lib.c_u32_p) if mask is not None else None, _p(Xs), _p(b),
-            _p(r) if r is not None else None, int(S), C.c_double(level), n_bins, _p(we) if we.size else None,
-            int(we.size), calib.ctypes.data_as(u64), brier.ctypes.data_as(u64), node_sums.ctypes.data_as(u64),
-            hist_width.ctypes.data_as(u64), _p(pw) if pointwise else None))
+            self._h, _p(bits), _po(mask), _p(Xs), _p(b), _po(r), int(S), C.c_double(level), n_bins, _po(we),
+            int(we.size), _p(calib), _p(brier), _p(node_sums), _p(hist_width), _po(pw)))
         return calib, brier, node_sums, hist_width, pw
 
     # -- tie dynamics (no reference counterpart) ---------------------------------------------------
@@ -1033,13 +1031,9 @@ class Chain(object):
         node_changes = np.zeros((U, self.N, 4), dtype=np.uint64)
         node_turnover = np.zeros((U, self.N, 2), dtype=np.uint64)
         pw = np.zeros((U, self.N, self.N, 4)) if pointwise else None
-        u64 = _lib.c_u64_p
         self._ck(self._L.dlsm_dynamics_accumulate(
-            self._h, bits.ctypes.data_as(_lib.c_u32_p),
-            mask.ctypes.data_as(_lib.c_u32_p) if mask is not None else None, _p(Xs), _p(b),
-            _p(r) if r is not None else None, int(S), int(min_count), n_bins, transitions.ctypes.data_as(u64),
-            hist_up.ctypes.data_as(u64), node_changes.ctypes.data_as(u64), node_turnover.ctypes.data_as(u64),
-            _p(pw) if pointwise else None))
+            self._h, _p(bits), _po(mask), _p(Xs), _p(b), _po(r), int(S), int(min_count), n_bins, _p(transitions),
+            _p(hist_up), _p(node_changes), _p(node_turnover), _po(pw)))
         return transitions, hist_up, node_changes, node_turnover, pw
 
     # -- multi-step posterior predictive forecasts (the reference: one step, undirected, on the host) ----
