@@ -21,6 +21,8 @@ from .convergence import convergence_diagnostics, ConvergenceResult  # noqa
 from .probabilities import edge_probabilities, EdgeProbabilityResult  # noqa
 from . import dynamics  # noqa
 from .dynamics import tie_dynamics, TieDynamicsResult  # noqa
+from . import community  # noqa
+from .community import community_structure, CommunityResult  # noqa
 from . import forecast  # noqa  (the one-step module; calling it is forecast_paths.forecast)
 from .forecast_paths import ForecastResult  # noqa
 
@@ -31,4 +33,4 @@ __all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
            'information_criteria', 'compare_information_criteria', 'ICResult', 'loo', 'compare_loo', 'LooResult',
            'in_sample_scores', 'ScoreResult', 'convergence_diagnostics', 'ConvergenceResult', 'forecast',
            'ForecastResult', 'edge_probabilities', 'EdgeProbabilityResult', 'dynamics', 'tie_dynamics',
-           'TieDynamicsResult']
+           'TieDynamicsResult', 'community', 'community_structure', 'CommunityResult']

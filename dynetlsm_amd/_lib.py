@@ -178,6 +178,8 @@ SIGNATURES = {
                                         c_u64_p, c_double_p]),
     'dlsm_dynamics_accumulate': (C.c_int, [handle_t, c_u32_p, c_u32_p, c_double_p, c_double_p, c_double_p, C.c_int,
                                            C.c_int, C.c_int, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_double_p]),
+    'dlsm_community_accumulate': (C.c_int, [handle_t, c_u32_p, c_u32_p, c_i64_p, C.c_int, C.c_int, C.c_int, c_i64_p,
+                                            c_i64_p, c_i64_p, c_i64_p, c_i64_p]),
     'dlsm_forecast_paths': (C.c_int, [handle_t, c_double_p, c_double_p, c_double_p, c_i32_p, c_double_p, c_double_p,
                                       c_double_p, c_double_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint64,
                                       C.c_uint32, C.c_int, c_double_p, c_double_p, c_i32_p]),

@@ -39,6 +39,7 @@
 #include "kernels_loo.hpp"
 #include "kernels_proba.hpp"
 #include "kernels_dynamics.hpp"
+#include "kernels_community.hpp"
 #include "kernels_missing.hpp"
 #include "host_draws.hpp"
 
@@ -2239,6 +2240,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_loo.hpp"
 #include "capi_proba.hpp"
 #include "capi_dynamics.hpp"
+#include "capi_community.hpp"
 #include "capi_forecast_paths.hpp"
 #include "capi_hdp.hpp"
 

@@ -1036,6 +1036,43 @@ class Chain(object):
             _p(hist_up), _p(node_changes), _p(node_turnover), _po(pw)))
         return transitions, hist_up, node_changes, node_turnover, pw
 
+    # -- community structure of stored labellings (the reference: modularity of one labelling on the host) ----
+    def community_accumulate(self, bits, zs, K, mask=None, batch=0, want_blocks=False):
+        """Counts of the labellings ``zs`` (S, T, N), integers in [0, K), 1 <= K <= 256, against the packed network
+        ``bits`` (``pack_network``; undirected chains: symmetric) without the excluded dyads ``mask`` (packed alike;
+        undirected chains: either orientation excludes the dyad), in one pass on the device
+        (csrc/kernels_community.hpp; the definition: include/dynetlsm_hip.h).  Every count is of ordered pairs.
+        Returns int64 tables: ``clusters`` (S, T, K, 5) - per labelling and cluster its nodes, the ties inside it,
+        its out-volume, its in-volume and the excluded ordered dyads inside it; ``node_within`` (T, N) - over the
+        samples, a node's ties into its own cluster; ``node_switch`` (T - 1, N) - the samples in which the node's
+        label changed; ``moved`` (S, T - 1) - the nodes whose label changed; and, with ``want_blocks``, ``blocks``
+        (S, T, K, K, 2) - ties and excluded ordered dyads from cluster a to cluster b - else None.  The labels are
+        staged ``batch`` samples at a time (0: automatic); no table depends on it."""
+        K, batch = int(K), int(batch)
+        if np.ndim(zs) != 3:
+            raise ValueError('zs must be (S, T, N), got %d dimensions' % np.ndim(zs))
+        zs = _i64(zs, (np.shape(zs)[0], self.T, self.N), 'zs')
+        S = zs.shape[0]
+        if S < 1:
+            raise ValueError('needs at least one sample')
+        if not 1 <= K <= 256:
+            raise ValueError('n_components must be in 1..256 (labels are kept as bytes), got %d' % K)
+        if batch < 0:
+            raise ValueError('batch must not be negative, got %d' % batch)
+        bits = self._packed(bits, 'bits')
+        if mask is not None:
+            mask = self._packed(mask, 'mask')
+        U = self.T - 1
+        clusters = np.zeros((S, self.T, K, 5), dtype=np.int64)
+        node_within = np.zeros((self.T, self.N), dtype=np.int64)
+        node_switch = np.zeros((U, self.N), dtype=np.int64)
+        moved = np.zeros((S, U), dtype=np.int64)
+        blocks = np.zeros((S, self.T, K, K, 2), dtype=np.int64) if want_blocks else None
+        self._ck(self._L.dlsm_community_accumulate(
+            self._h, _p(bits), _po(mask), _p(zs), S, K, batch, _p(clusters), _p(node_within), _po(node_switch),
+            _po(moved), _po(blocks)))
+        return clusters, node_within, node_switch, moved, blocks
+
     # -- multi-step posterior predictive forecasts (the reference: one step, undirected, on the host) ----
     def forecast_paths(self, X0, intercepts, radii=None, z0=None, trans=None, mu=None, sigma=None, lmbda=None,
                        sigma_sq=0.0, horizon=1, seed=0, first_index=0, batch=0, want_paths=False,

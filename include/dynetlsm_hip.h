@@ -583,6 +583,30 @@ int dlsm_dynamics_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t
                              uint64_t *transitions, uint64_t *hist_up, uint64_t *node_changes,
                              uint64_t *node_turnover, double *pointwise);
 
+/* ---- community structure of stored labellings ---------------------------- */
+/* The reference has modularity(Y, z) for one labelling on the host (network_statistics.py:31-61); the rest has no
+ * counterpart.  zs S*T*N int64 labels in [0, K), 1 <= K <= 256 (packed to bytes on the device, staged in batches of
+ * `batch` samples, 0: automatic; no table depends on it); bits T*N*W uint32 the packed network (undirected handles:
+ * symmetric), mask NULL or the excluded dyads packed alike - its diagonal and padding bits are ignored, and on an
+ * undirected handle a dyad is excluded when either of (i, j), (j, i) is set.  A tie is a set bit (i, j) of `bits` whose
+ * dyad is not excluded; every count is of ordered pairs (an undirected tie counts twice).  With a = z[s][t][i]:
+ *   clusters     S*T*K*5 int64, per labelling (s, t) and cluster a: the nodes with label a; the ties (i, j) with
+ *                z_i = z_j = a; the out-volume, ties (i, j) with z_i = a; the in-volume, ties (i, j) with z_j = a
+ *                (undirected: the out-volume again); the excluded ordered dyads i != j with z_i = z_j = a
+ *   node_within  T*N int64: over the S samples, the ties (i, j) of node i with z_j = z_i
+ *   node_switch  (T-1)*N int64: the samples with z[s][t+1][i] != z[s][t][i]
+ *   moved        S*(T-1) int64: the nodes i with z[s][t+1][i] != z[s][t][i]
+ *                (T = 1: both are empty and may be NULL)
+ *   blocks       NULL or S*T*K*K*2 int64: per labelling and ordered pair of clusters (a, b) the ties (i, j) with
+ *                z_i = a, z_j = b, and the excluded ordered dyads i != j with z_i = a, z_j = b
+ * Everything added across workgroups is an integer added with an atomic: the same call returns the same tables,
+ * whatever the order and the batch.  S < 1, K outside 1..256, batch < 0 -> DLSM_E_ARG; a label outside [0, K), a set
+ * diagonal or padding bit of `bits`, an undirected network that is not symmetric -> DLSM_E_DATA, all before any
+ * device work; N beyond what a workgroup's LDS holds of labels (some 40 000) -> DLSM_E_LIMIT. */
+int dlsm_community_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *mask, const int64_t *zs, int S,
+                              int K, int batch, int64_t *clusters, int64_t *node_within, int64_t *node_switch,
+                              int64_t *moved, int64_t *blocks);
+
 /* ---- multi-step posterior predictive forecasts --------------------------- */
 /* The reference has only the one-step undirected form (hdp_lpcm.py:555-626, drawn on the host).  One
  * trajectory of H future time steps per sample s, started at the sample's last time step X0 S*N*D:
