@@ -17,19 +17,15 @@ import time
 
 import numpy as np
 
-from .engine import Chain, SamplerGrid, check_n_features
+from .engine import check_n_features
+from . import _fit
 from . import hdp_updates as hu
-from . import initialization as init_mod
 from . import posterior as post
 from . import forecast as fc
 from .diagnostics import geweke_diag
-from .imputer import SimpleNetworkImputer
-from .metrics import FittedQuantities, missing_index
-from .lsm import (DynamicNetworkLSM, _ScalarMetropolis, _dirichlet_logpdf,
-                  _missing_attributes, check_random_state)
+from ._fit import Estimator, _ScalarMetropolis, _missing_attributes, check_random_state
 
 __all__ = ['DynamicNetworkHDPLPCM']
-
 
 
 def _geweke(trace, n_burn):
@@ -42,7 +38,7 @@ def _geweke(trace, n_burn):
         return float('nan'), float('nan')
 
 
-class DynamicNetworkHDPLPCM(FittedQuantities):
+class DynamicNetworkHDPLPCM(Estimator):
     """Constructor parameters are the reference's (hdp_lpcm.py:385-455) plus
     ``device``, ``chain_id``, ``sweep_algo`` and ``hdp_loop``:
 
@@ -123,14 +119,6 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
         return (self.burn or 0) + (self.tune or 0)
 
     # -- one-step-ahead forecasts (hdp_lpcm.py:496-626; undirected models) ----------
-    def _forecast_ready(self):
-        if not hasattr(self, 'X_'):
-            raise ValueError('Model not fit.')
-        if self.is_directed:
-            raise ValueError('forecasts are implemented for undirected models '
-                             '(as the reference formulas are)')
-        return self.chain_
-
     @property
     def forecast_probas_map_(self):
         return fc.forecast_probas_map(self, self._forecast_ready())
@@ -150,51 +138,6 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
     def forecast_probas_pp_(self):
         return fc.forecast_probas_pp(self, self._forecast_ready())
 
-    def forecast(self, horizon=1, **kw):
-        """posterior predictive forecast of the next ``horizon`` networks, drawn on the device; undirected and
-        directed fits (``forecast_paths.forecast``)"""
-        from .forecast_paths import forecast
-        return forecast(self, horizon=horizon, **kw)
-
-    # ------------------------------------------------------------------ init
-    def _init_sampler(self, Y, rng, init):
-        """hdp_lpcm.py:48-141 : LSM warm start, longitudinal k-means, weights"""
-        T, N, _ = Y.shape
-        K, D = self.n_components, check_n_features(self.n_features)
-        if init is not None and 'X' in init:
-            X = np.array(init['X'], dtype=np.float64)
-            intercept = np.atleast_1d(np.asarray(init['intercept'], dtype=np.float64)).copy()
-            radii = np.array(init['radii'], dtype=np.float64) if self.is_directed else None
-        else:
-            kw = (dict(sigma_sq=0.001, tau_sq='auto', step_size_X=0.0075,
-                       n_control=self.n_control, n_resample_control=self.n_resample_control)
-                  if self.is_directed else dict(sigma_sq=0.1, tau_sq=2.0, step_size_X=0.1))
-            emb = DynamicNetworkLSM(n_iter=500, n_features=D, tune=250, burn=250,
-                                    is_directed=self.is_directed, random_state=rng,
-                                    device=self.device, chain_id=self.chain_id,
-                                    sweep_algo=self.sweep_algo, **kw).fit(Y)
-            X, intercept = emb.X_.copy(), np.array(emb.intercept_, dtype=np.float64)
-            radii = emb.radii_.copy() if self.is_directed else None
-            emb.chain_.close()
-        if init is not None and 'mu' in init:
-            mu = np.array(init['mu'], dtype=np.float64)
-            sigma = np.array(init['sigma'], dtype=np.float64)
-            z = np.array(init['z'], dtype=np.int64)
-        else:
-            # the Lloyd iterations of longitudinal_kmeans run on the device (any handle will do)
-            with Chain(1, N, D, 'undirected', device=self.device) as tmp:
-                mu, sigma, z = init_mod.longitudinal_kmeans(X, n_clusters=K, random_state=rng,
-                                                            chain=tmp)
-            z = z.astype(np.int64)
-        weights = np.zeros((T, K, K))
-        weights[0, 0] = np.bincount(z[0], minlength=K) / N
-        lmbda = np.array([self.lambda_prior], dtype=np.float64)
-        beta = rng.dirichlet(np.repeat(self.gamma / K, K))
-        for t in range(1, T):
-            for k in range(K):
-                weights[t, k] = rng.dirichlet(self.alpha * beta + self.kappa * np.eye(K)[k])
-        return X, intercept, mu, sigma, z, beta, weights, lmbda, radii
-
     # ------------------------------------------------------------------- fit
     def fit(self, Y, init=None):
         """Sample the posterior of the HDP-LPCM given ``Y`` (T, N, N).  ``init``
@@ -212,112 +155,49 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
         ``network_from``: callable(chain) that loads the network into the chain some other
         way than the float64 upload (multi-GPU: the packed broadcast of multichain)."""
         # (copy=False keeps the caller's array as it is - a network_from loader never reads it)
-        Y = (np.array(Y, dtype=np.float64, order='C') if self.copy or network_from is None
-             else np.asarray(Y, dtype=np.float64))
-        if Y.ndim != 3 or Y.shape[1] != Y.shape[2]:
-            raise ValueError('Y must have shape (n_time_steps, n_nodes, n_nodes)')
-        if np.any(np.isnan(Y)):
-            raise ValueError('NaN entries are not supported: code missing dyads as -1')
-        # missing dyads (hdp_lpcm.py:669-706): imputed once; undirected models also average
-        # per-iteration Bernoulli draws of them after burn-in into ``missings_``
-        self.nan_mask_, miss = None, None
-        if self.sample_missing and self.n_control is not None:
-            raise ValueError('sample_missing=True is not supported with n_control: the case-control '
-                             'chain holds edge lists and control samples, not the dyads to re-draw')
+        Y = _fit.check_network(Y, True if self.copy or network_from is None else None)
+        _fit.check_options(self)
         if self.sample_missing and self.hdp_loop == 'device':
             raise ValueError("sample_missing=True runs on the host-driven loop: hdp_loop='device' "
                              'has no imputation step')
-        # sample_missing=True: the dyads are drawn on the device instead and written into the chain's
-        # network (Chain.impute_missing), from the host-driven loop; no host draws then
-        self._miss_index = None
-        if self.sample_missing and np.any(Y == -1):
-            self._miss_index = missing_index(Y, self.is_directed)
-        if np.any(Y == -1):
-            if not self.is_directed:
-                iu = np.nonzero(np.triu(np.ones(Y.shape, dtype=bool), 1))
-                self.nan_mask_ = Y[iu] == -1
-                if self._miss_index is None:
-                    miss = np.nonzero(np.triu(Y == -1, 1))        # (t, i, j), row-major
-                    self.missings_ = np.zeros(miss[0].shape[0])
-            else:
-                off = np.nonzero(~np.eye(Y.shape[1], dtype=bool)[None].repeat(Y.shape[0], 0))
-                self.nan_mask_ = Y[off] == -1
-            Y = SimpleNetworkImputer(strategy='random', missing_value=-1).fit_transform(Y)
         if self.selection_type not in ('vi', 'bic', 'map'):
             raise ValueError('Selection type not recognized')
-        if self.n_control is not None and not self.is_directed:
-            raise ValueError('The case-control likelihood currently only '
-                             'supported for directed networks.')
+        # missing dyads (hdp_lpcm.py:669-706): imputed once; undirected models also average
+        # per-iteration Bernoulli draws of them after burn-in into ``missings_``, unless
+        # sample_missing=True has the device draw them (Chain.impute_missing)
+        Y, miss, self._miss_index = _fit.prepare_missing(self, Y)
         T, N, _ = Y.shape
         K, D = self.n_components, check_n_features(self.n_features)
         rng = check_random_state(self.random_state)
         self.Y_fit_ = Y
-        if self.burn is not None:
-            self.n_iter += self.burn
-        if self.tune is not None:
-            self.n_iter += self.tune
-        n_total = self.n_iter
+        n_total = _fit.extend_n_iter(self)
 
-        (X, intercept, mu, sigma, z, beta, weights, lmbda, radii) = \
-            self._init_sampler(Y, rng, init)
-        if isinstance(self.step_size_X, str) and self.step_size_X == 'auto':
-            self.step_size_X = 0.01 if self.is_directed else 0.1
-        if isinstance(self.intercept_prior, str) and self.intercept_prior == 'auto':
-            self.intercept_prior = intercept.copy()
-        ip = np.atleast_1d(np.asarray(self.intercept_prior, dtype=np.float64))
+        # starting values (hdp_lpcm.py:48-141): LSM warm start, longitudinal k-means, weights
+        Y, X, intercept, radii, mu, sigma, z = _fit.warm_start(self, Y, rng, init,
+                                                               kmeans_on_device=True)
+        weights = np.zeros((T, K, K))
+        weights[0, 0] = np.bincount(z[0], minlength=K) / N
+        lmbda = np.array([self.lambda_prior], dtype=np.float64)
+        beta = rng.dirichlet(np.repeat(self.gamma / K, K))
+        for t in range(1, T):
+            for k in range(K):
+                weights[t, k] = rng.dirichlet(self.alpha * beta + self.kappa * np.eye(K)[k])
 
         # hyper-priors (hdp_lpcm.py:760-793)
-        if isinstance(self.mean_variance_prior, str) and self.mean_variance_prior == 'auto':
-            mvp = (2 * (1. / N) ** (2. / D) if self.is_directed else (N ** (2. / D)) / 50.)
-        else:
-            mvp = self.mean_variance_prior
-        hp = hu.HDPHyper(K, gamma=self.gamma, alpha_init=self.alpha_init, alpha=self.alpha,
-                         kappa=self.kappa, mean_variance_prior=mvp, a=self.a,
-                         lambda_prior=self.lambda_prior,
-                         lambda_variance_prior=self.lambda_variance_prior,
-                         gamma_prior_shape=self.gamma_prior_shape,
-                         gamma_prior_rate=self.gamma_prior_rate,
-                         alpha_init_shape=self.alpha_init_shape,
-                         alpha_init_rate=self.alpha_init_rate,
-                         alpha_kappa_shape=self.alpha_kappa_shape,
-                         alpha_kappa_rate=self.alpha_kappa_rate)
-        if self.mean_variance_prior_std is not None:
-            hp.a0 = (self.mean_variance_prior_std ** 2 + 2) * 2
-            hp.b0 = (hp.a0 - 2) * mvp * 2
-        hp.b = (self.a + 2) * mvp if (isinstance(self.b, str) and self.b == 'auto') else self.b
-        if self.sigma_prior_std is not None:
-            hp.d0 = (self.sigma_prior_std ** 2 / hp.b) * 2
-            hp.c0 = hp.b * hp.d0
+        hp, ip = _fit.mixture_hyper(
+            self, N, D, intercept, gamma=self.gamma, alpha_init=self.alpha_init, alpha=self.alpha,
+            kappa=self.kappa, gamma_prior_shape=self.gamma_prior_shape,
+            gamma_prior_rate=self.gamma_prior_rate, alpha_init_shape=self.alpha_init_shape,
+            alpha_init_rate=self.alpha_init_rate, alpha_kappa_shape=self.alpha_kappa_shape,
+            alpha_kappa_rate=self.alpha_kappa_rate)
         self.hyper_ = hp
 
-        # ---- the chain -----------------------------------------------------
-        model = ('undirected' if not self.is_directed else
-                 'case_control' if self.n_control is not None else 'directed')
-        seed = int(rng.randint(0, 2 ** 31 - 1)) | (int(rng.randint(0, 2 ** 31 - 1)) << 31)
-        chain = Chain(T, N, D, model, seed=seed, chain_id=self.chain_id, device=self.device)
-        self.chain_ = chain
-        self.case_control_sampler_ = None
-        if model == 'case_control':
-            from .case_control import DirectedCaseControlSampler
-            self.case_control_sampler_ = DirectedCaseControlSampler(
-                n_control=self.n_control, n_resample=self.n_resample_control,
-                chain=chain).init(Y)
-        elif network_from is not None:
-            network_from(chain)
-        else:
-            chain.upload_network(Y)
-        chain.set_positions(X)
-        chain.set_intercepts(intercept)
-        if self.is_directed:
-            chain.set_radii(radii)
-        self.latent_samplers = SamplerGrid(T, N, self.step_size_X, tune=self.tune,
-                                           tune_interval=self.tune_interval)
-        chain.set_samplers(self.latent_samplers)
+        chain = _fit.open_chain(self, Y, X, intercept, radii, _fit.chain_seed(rng), network_from)
         n_ic = 2 if self.is_directed else 1
         # hdp_lpcm.py:731-747: intercept samplers keep the default tune_interval
-        isamp = [_ScalarMetropolis(self.step_size_intercept, self.tune) for _ in range(n_ic)]
-        rsamp = _ScalarMetropolis(self.step_size_radii, self.tune, dirichlet=True)
-        self.intercept_samplers, self.radii_sampler = isamp, rsamp
+        self.intercept_samplers = [_ScalarMetropolis(self.step_size_intercept, self.tune)
+                                   for _ in range(n_ic)]
+        self.radii_sampler = _ScalarMetropolis(self.step_size_radii, self.tune, dirichlet=True)
 
         if self.hdp_loop not in ('auto', 'device', 'host'):
             raise ValueError("hdp_loop must be 'auto', 'device' or 'host'")
@@ -406,65 +286,22 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
         the kernels of the engine around numpy draws on the caller's MT19937 stream."""
         chain, rng, hp, ip = self.chain_, self._rng, self.hyper_, self._ip
         if self.loop_kind_ == 'device-resident':
-            ccs = self.case_control_sampler_
-            if ccs is None:
-                chain.hdp_run(first, count)      # asynchronous: the iterations are enqueued
-                return
-            # the host keeps the cadence of the control resampling (case_control_likelihood.py:27-33)
-            it, last = first, first + count - 1
-            while it <= last:
-                ccs.resample(it)
-                nxt = it + 1
-                while nxt <= last and (ccs.n_resample is None or ccs.n_iter % ccs.n_resample != 0):
-                    ccs.n_iter += 1
-                    nxt += 1
-                chain.hdp_run(it, nxt - it)
-                it = nxt
+            # asynchronous: the iterations are enqueued
+            _fit.run_ranges(self.case_control_sampler_, first, first + count - 1, chain.hdp_run)
             return
         isamp, rsamp, sums, miss = (self.intercept_samplers, self.radii_sampler, self._sums,
                                     self._miss)
         st = self._st
         X, intercept, mu, sigma, z = st['X'], st['intercept'], st['mu'], st['sigma'], st['z']
         beta, weights, lmbda, radii = st['beta'], st['weights'], st['lmbda'], st['radii']
-        n_ic = 2 if self.is_directed else 1
-        var = self.intercept_variance_prior
         for it in range(first, first + count):
             if self.case_control_sampler_ is not None:
                 self.case_control_sampler_.resample(it)
             chain.set_prior_mixture(mu, sigma, lmbda, None)      # z: the device keeps its own
             chain.sweep_positions(it, self.sweep_algo)
             chain.center()
-            # intercepts (sample_coefficients.py:12-88), fused two-candidate passes
-            for k in range(n_ic):
-                prop = intercept.copy()
-                prop[k] = intercept[k] + isamp[k].step_size * rng.randn(1)[0]
-                if k == 0:
-                    ll_prop, ll_cur = chain.loglik_full([prop, intercept])
-                else:       # same positions, and `intercept` is the state the last step left:
-                    ll_prop, ll_cur = chain.loglik_full([prop])[0], ll      # its value is known
-                ratio = ((ll_prop - (prop[k] - ip[k]) ** 2 / (2 * var)) -
-                         (ll_cur - (intercept[k] - ip[k]) ** 2 / (2 * var)))
-                accepted = int(not (np.log(rng.rand()) >= ratio))
-                ll = ll_cur
-                if accepted:
-                    intercept, ll = prop, ll_prop
-                isamp[k].book(accepted)
-            chain.set_intercepts(intercept)
-            if self.is_directed:
-                x = rng.dirichlet(rsamp.step_size * radii)
-                if np.any(x == 0.):
-                    x += 1e-5
-                    x /= np.sum(x)
-                ll_cur, ll_prop = chain.loglik_full_radii(x)
-                ratio = (ll_prop - ll_cur +
-                         _dirichlet_logpdf(radii, rsamp.step_size * x) -
-                         _dirichlet_logpdf(x, rsamp.step_size * radii))
-                accepted = int(not (np.log(rng.rand()) >= ratio))
-                ll = ll_cur
-                if accepted:
-                    radii, ll = x, ll_prop
-                    chain.set_radii(radii)
-                rsamp.book(accepted)
+            intercept, radii, ll = _fit.coefficient_steps(
+                chain, rng, intercept, radii, ip, self.intercept_variance_prior, isamp, rsamp)
             # label block update on the device (sample_labels.py:134-190)
             z, n, nk = chain.sample_labels(it, weights)
             X = chain.get_positions()
@@ -473,9 +310,7 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
             if self._miss_index is not None:      # hdp_lpcm.py:1039-1049, with the draw written back
                 chain.impute_missing(it, it > self.n_burn_)
             if miss is not None:                  # hdp_lpcm.py:1039-1049
-                dm = X[miss[0], miss[1]] - X[miss[0], miss[2]]
-                eta = intercept[0] - np.sqrt(np.sum(dm * dm, axis=1))
-                y_ij = rng.binomial(1, 1. / (1. + np.exp(-eta)))
+                y_ij = _fit.draw_missing(rng, X, intercept[0], miss)
                 if it > self.n_burn_:
                     self.missings_ += y_ij
             st.update(X=X, intercept=intercept, mu=mu, sigma=sigma, z=z, beta=beta,
@@ -546,12 +381,7 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
         self.lambdas_, self.hypers_ = tr['lambdas'], tr['hypers']
         self._trace_logliks = tr['logliks']
         self._lazy_trace = True
-        cfg = chain.hdp_get_config()
-        hp.gamma, hp.alpha_init, hp.alpha, hp.kappa = cfg.gamma, cfg.alpha_init, cfg.alpha, cfg.kappa
-        hp.mean_variance_prior, hp.b = cfg.mean_variance_prior, cfg.b
-        sm = self.intercept_samplers[0]
-        sm.step_size, sm.n_accepted = cfg.i_step_size, cfg.i_n_accepted
-        sm.n_steps, sm.steps_until_tune = cfg.i_n_steps, cfg.i_steps_until_tune
+        _fit.samplers_from_hdp_config(self, chain.hdp_get_config())
         last = post._trace_row(chain, n_total - 1)
         self._st.update(X=last['X'], intercept=last['intercept'], mu=last['mu'], sigma=last['sigma'],
                         z=last['z'], beta=last['beta'], weights=last['weights'], lmbda=last['lmbda'])
@@ -584,30 +414,16 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
             return self._finish_on_device()
         if self.loop_kind_ == 'device-resident':
             self._pull(1, n_total - 1)
-            cfg = chain.hdp_get_config()
-            hp.gamma, hp.alpha_init, hp.alpha, hp.kappa = (cfg.gamma, cfg.alpha_init, cfg.alpha,
-                                                           cfg.kappa)
-            hp.mean_variance_prior, hp.b = cfg.mean_variance_prior, cfg.b
-            sm = self.intercept_samplers[0]
-            sm.step_size, sm.n_accepted = cfg.i_step_size, cfg.i_n_accepted
-            sm.n_steps, sm.steps_until_tune = cfg.i_n_steps, cfg.i_steps_until_tune
+            _fit.samplers_from_hdp_config(self, chain.hdp_get_config())
             self._st.update(X=self.Xs_[-1], intercept=self.intercepts_[-1], mu=self.mus_[-1],
                             sigma=self.sigmas_[-1], z=self.zs_[-1], beta=self.betas_[-1],
                             weights=self.weights_[-1], lmbda=self.lambdas_[-1])
             if self.is_directed:
-                so, rs = self.intercept_samplers[1], self.radii_sampler
-                so.step_size, so.n_accepted = cfg.i_step_size_out, cfg.i_n_accepted_out
-                so.n_steps, so.steps_until_tune = cfg.i_n_steps_out, cfg.i_steps_until_tune_out
-                rs.step_size, rs.n_accepted = cfg.r_step_size, cfg.r_n_accepted
-                rs.n_steps, rs.steps_until_tune = cfg.r_n_steps, cfg.r_steps_until_tune
                 self._st.update(radii=self.radiis_[-1])
             if self._miss is not None:            # hdp_lpcm.py:1039-1049 from the stored samples
-                miss, rng = self._miss, self._rng
                 for it in range(1, n_total):
-                    X = self.Xs_[it]
-                    dm = X[miss[0], miss[1]] - X[miss[0], miss[2]]
-                    eta = self.intercepts_[it, 0] - np.sqrt(np.sum(dm * dm, axis=1))
-                    y_ij = rng.binomial(1, 1. / (1. + np.exp(-eta)))
+                    y_ij = _fit.draw_missing(self._rng, self.Xs_[it], self.intercepts_[it, 0],
+                                             self._miss)
                     if it > self.n_burn_:
                         self.missings_ += y_ij
         if self._miss is not None:
@@ -620,12 +436,8 @@ class DynamicNetworkHDPLPCM(FittedQuantities):
         self.mean_variance_prior_, self.b_ = hp.mean_variance_prior, hp.b
 
         # thinning (hdp_lpcm.py:1072-1083)
-        if self.thin is not None:
-            for name in ('Xs_', 'intercepts_', 'mus_', 'sigmas_', 'zs_', 'betas_',
-                         'weights_', 'lambdas_', 'logps_'):
-                setattr(self, name, getattr(self, name)[::self.thin])
-            if self.is_directed:
-                self.radiis_ = self.radiis_[::self.thin]
+        _fit.thin_traces(self, ('Xs_', 'intercepts_', 'mus_', 'sigmas_', 'zs_', 'betas_',
+                                'weights_', 'lambdas_', 'logps_'))
         # model selection (hdp_lpcm.py:1085-1139): BIC / MAP size / minimum posterior
         # expected VI, with the co-occurrence matrices and the VI criterion on the device
         n_burn = min(-(-self.n_burn_ // (self.thin or 1)), self.logps_.shape[0] - 1)     # ceil: hdp_lpcm.py:465
