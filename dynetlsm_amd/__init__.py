@@ -19,6 +19,8 @@ from .loo import loo, compare_loo, LooResult  # noqa
 from .scores import in_sample_scores, ScoreResult  # noqa
 from .convergence import convergence_diagnostics, ConvergenceResult  # noqa
 from .probabilities import edge_probabilities, EdgeProbabilityResult  # noqa
+from . import ranking  # noqa
+from .ranking import top_dyads, TopDyadsResult  # noqa
 from . import dynamics  # noqa
 from .dynamics import tie_dynamics, TieDynamicsResult  # noqa
 from . import community  # noqa
@@ -33,4 +35,5 @@ __all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
            'information_criteria', 'compare_information_criteria', 'ICResult', 'loo', 'compare_loo', 'LooResult',
            'in_sample_scores', 'ScoreResult', 'convergence_diagnostics', 'ConvergenceResult', 'forecast',
            'ForecastResult', 'edge_probabilities', 'EdgeProbabilityResult', 'dynamics', 'tie_dynamics',
-           'TieDynamicsResult', 'community', 'community_structure', 'CommunityResult']
+           'TieDynamicsResult', 'community', 'community_structure', 'CommunityResult', 'ranking', 'top_dyads',
+           'TopDyadsResult']

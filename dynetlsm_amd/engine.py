@@ -45,6 +45,17 @@ def pack_network(Y):
     return np.ascontiguousarray(bytes_).view('<u4').astype(np.uint32).reshape(T, N, W)
 
 
+def rank_candidates(index, value, k, largest=True):
+    """The first ``k`` of the candidates of one time step as ``dlsm_topk_accumulate`` wrote them - ``index`` (n, 4)
+    int32 rows (i, j, y, 0), ``value`` (n, 2) rows (proba, sd), in any order - by (proba descending - ascending
+    unless ``largest`` -, then i, then j): the tuple (i, j, y, proba, sd) of arrays in rank order"""
+    ij = index[:, 0].astype(np.int64) * (1 << 31) + index[:, 1]
+    order = np.lexsort((ij, -value[:, 0] if largest else value[:, 0]))[:k]
+    index, value = index[order].astype(np.int64), value[order]
+    return (np.ascontiguousarray(index[:, 0]), np.ascontiguousarray(index[:, 1]), np.ascontiguousarray(index[:, 2]),
+            np.ascontiguousarray(value[:, 0]), np.ascontiguousarray(value[:, 1]))
+
+
 def check_missing_index(index, T, N, model):
     """(n, 3) int32 rows (t, i, j) of missing dyads, validated as ``dlsm_set_missing`` validates them
     (ValueError, before any device call)"""
@@ -997,6 +1008,61 @@ class Chain(object):
             self._h, _p(bits), _po(mask), _p(Xs), _p(b), _po(r), int(S), C.c_double(level), n_bins, _po(we),
             int(we.size), _p(calib), _p(brier), _p(node_sums), _p(hist_width), _po(pw)))
         return calib, brier, node_sums, hist_width, pw
+
+    # -- link prediction (no reference counterpart) ------------------------------------------------
+    TOPK_AMONG = ('non_ties', 'ties', 'observed', 'missing', 'all')
+
+    def topk_accumulate(self, bits, Xs, intercepts, radii, k, among='non_ties', largest=True, mask=None,
+                        max_candidates=None):
+        """Per time step the ``k`` eligible dyads that come first by the posterior-mean edge probability over the
+        S >= 2 samples (arguments as ``proba_accumulate``): probability descending, then i, then j; ``largest=False``:
+        ascending, then i, then j.  Selected on the device without a (T, N, N) array or a sort of it
+        (csrc/kernels_topk.hpp; the definition: include/dynetlsm_hip.h).  ``among``: ``'non_ties'`` - dyads that
+        ``mask`` does not exclude with y = 0 in ``bits`` -, ``'ties'`` - not excluded, y = 1 -, ``'observed'`` - not
+        excluded -, ``'missing'`` - the dyads that ``mask`` excludes - or ``'all'``.  The device returns every dyad
+        that shares the rank key of the k-th or lies beyond it, at most ``max_candidates`` (default ``k + 2**20``)
+        per time step, else ``EngineError`` with code -5; they are sorted here and cut to k.  Returns ``steps``, per
+        time step a tuple (i, j, y, proba, sd) of arrays of min(k, eligible) entries in rank order, and ``diag``, a
+        dict of (T,) int64 arrays: ``eligible``, ``n_beyond`` and ``n_at`` (dyads beyond and at the k-th key),
+        ``key`` (-1: nothing eligible), ``tiles_revisited`` (tiles of the second pass), and ``n_tiles``, the tiles of
+        a time step."""
+        if among not in self.TOPK_AMONG:
+            raise ValueError('among must be one of %s, got %r' % (', '.join(map(repr, self.TOPK_AMONG)), among))
+        if int(k) != k or int(k) < 1:
+            raise ValueError('k must be a positive integer, got %r' % (k,))
+        k = int(k)
+        if max_candidates is None:
+            max_candidates = k + 2 ** 20
+        if int(max_candidates) != max_candidates or int(max_candidates) < k:
+            raise ValueError('max_candidates must be an integer >= k=%d, got %r' % (k, max_candidates))
+        bits = self._packed(bits, 'bits')
+        if mask is not None:
+            mask = self._packed(mask, 'mask')
+        elif among == 'missing':
+            raise ValueError("among='missing' needs the mask of the missing dyads")
+        if np.shape(Xs)[0] < 2:
+            raise ValueError('needs at least two samples (the standard deviation has ddof = 1)')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii)
+        T, N = self.T, self.N
+        dyads = N * (N - 1) // (1 if self.model != UNDIRECTED else 2)
+        # no time step has more candidates than dyads: room beyond that (and beyond k) is never used
+        room = min(int(max_candidates), max(k, dyads))
+        index = np.zeros((T, room, 4), dtype=np.int32)
+        value = np.zeros((T, room, 2))
+        n_cand = np.zeros(T, dtype=np.int32)
+        diag = np.zeros((T, 5), dtype=np.int64)
+        self._ck(self._L.dlsm_topk_accumulate(
+            self._h, _p(bits), _po(mask), _p(Xs), _p(b), _po(r), int(S), self.TOPK_AMONG.index(among),
+            int(bool(largest)), C.c_int64(k), C.c_int64(room), _p(index), _p(value), _p(n_cand), _p(diag)))
+        steps = [rank_candidates(index[t, :int(n_cand[t])], value[t, :int(n_cand[t])], k, largest) for t in range(T)]
+        tile_rows = 32 if self.D <= 4 else 16
+        n_rb, n_cb = -(-N // tile_rows), -(-N // 64)
+        if self.model != UNDIRECTED:
+            n_tiles = n_rb * n_cb
+        else:
+            n_tiles = sum(1 for bi in range(n_rb) for bj in range(n_cb) if bi * tile_rows < min(N, (bj + 1) * 64) - 1)
+        return steps, dict(eligible=diag[:, 0].copy(), n_beyond=diag[:, 1].copy(), n_at=diag[:, 2].copy(),
+                           key=diag[:, 3].copy(), tiles_revisited=diag[:, 4].copy(), n_tiles=n_tiles)
 
     # -- tie dynamics (no reference counterpart) ---------------------------------------------------
     def dynamics_accumulate(self, bits, Xs, intercepts, radii, min_count, mask=None, n_bins=20, pointwise=False):

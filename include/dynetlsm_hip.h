@@ -583,6 +583,42 @@ int dlsm_dynamics_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t
                              uint64_t *transitions, uint64_t *hist_up, uint64_t *node_changes,
                              uint64_t *node_turnover, double *pointwise);
 
+/* ---- link prediction (top-k dyads by posterior edge probability) --------- */
+/* No reference counterpart (probas_ of one selected sample and a dense argsort on the host).  For every time step t,
+ * over the eligible dyads of the handle (undirected: i < j; directed and case-control: i != j), with
+ *   pbar(t, i, j) = (1/S) sum_s expit(eta_s)      (eta and the samples Xs S*T*N*D, intercepts S*2, radii S*N or NULL as
+ *                                                  dlsm_score_accumulate takes them; s = 0 .. S-1 in order)
+ * the dyads that can be among the k first in the total order (pbar descending, i ascending, j ascending; largest = 0:
+ * pbar ascending, i, j) are returned, each with its pbar, the standard deviation (ddof 1, Welford) of p_s =
+ * expit(eta_s) and its bit y of the packed network `bits` (T*N*W uint32).  Eligible (`among`), with "observed" = the
+ * dyad's bit of `mask` (NULL, or T*N*W uint32 packed like the network; undirected handles: either of (i, j), (j, i))
+ * is not set:
+ *   0 observed and y = 0 (predicted links)    1 observed and y = 1 (implausible ties)    2 observed
+ *   3 masked (needs `mask`)                   4 every dyad
+ * Selection is by the rank key of dlsm_score_accumulate, key = max(bits((float)pbar) >> 8, 0x200000), which never
+ * decreases with pbar: a first pass over the samples counts the keys of the eligible dyads per time step into a
+ * histogram in device memory (time steps in groups, within a fixed budget) and keeps the extreme key of every tile of
+ * 32 x 64 dyads (n_features > 4: 16 x 64); a scan finds the key kappa_t with
+ *   n_beyond_t = count(keys beyond kappa_t) < k <= n_beyond_t + n_at_t,   n_at_t = count(keys equal to kappa_t)
+ * (fewer than k eligible dyads: kappa_t is the last key that is not empty, and all of them are returned); a second
+ * pass over the tiles whose extreme key reaches kappa_t writes the n_beyond_t + n_at_t dyads whose key does.  The
+ * caller sorts them by (pbar, i, j) and keeps k: they are written in no particular order.  Nothing of size T*N*N is
+ * stored or sorted.
+ *   cand_index  T*max_candidates*4 int32: (i, j, y, 0) of the dyads of time step t in its first n_cand[t] rows
+ *   cand_value  T*max_candidates*2: (pbar, sd) of the same rows
+ *   n_cand      T int32: = n_beyond_t + n_at_t
+ *   diag        T*5 int64: eligible_t, n_beyond_t, n_at_t, kappa_t (-1: no eligible dyad) and the tiles of the time step
+ *               that the second pass visited
+ * The counts are exact integers and both passes form pbar with the same instructions: the same call returns the same
+ * set of rows.  S < 2, among outside 0..4, largest not 0 or 1, k < 1, max_candidates < k, among = 3 without a mask ->
+ * DLSM_E_ARG; a set diagonal or padding bit of `bits`, a radius <= 0 -> DLSM_E_DATA.  n_beyond_t + n_at_t >
+ * max_candidates for some t (more dyads share the key of the k-th than there is room for; the message names t, the
+ * count and max_candidates), 2^31 or more dyads per time step, or samples that do not fit the device -> DLSM_E_LIMIT. */
+int dlsm_topk_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *mask, const double *Xs,
+                         const double *intercepts, const double *radii, int S, int among, int largest, int64_t k,
+                         int64_t max_candidates, int32_t *cand_index, double *cand_value, int32_t *n_cand,
+                         int64_t *diag);
+
 /* ---- community structure of stored labellings ---------------------------- */
 /* The reference has modularity(Y, z) for one labelling on the host (network_statistics.py:31-61); the rest has no
  * counterpart.  zs S*T*N int64 labels in [0, K), 1 <= K <= 256 (packed to bytes on the device, staged in batches of
@@ -683,7 +719,10 @@ enum {
     DLSM_K_SCORE_ACCUMULATE = 9,   /* dlsm_score_accumulate: k_score_accumulate (sample loop + histogram) */
     DLSM_K_SCORE_CLEAR = 10,       /* ... the histograms' hipMemsetAsync */
     DLSM_K_SCORE_SCAN = 11,        /* ... k_score_scan (pooling included) and the log-loss reduction */
-    DLSM_K_COUNT = 12
+    DLSM_K_TOPK_COUNT = 12,        /* dlsm_topk_accumulate: k_topk_count and the histograms' hipMemsetAsync */
+    DLSM_K_TOPK_SCAN = 13,         /* ... k_topk_threshold */
+    DLSM_K_TOPK_EMIT = 14,         /* ... k_topk_emit */
+    DLSM_K_COUNT = 15
 };
 /* when enabled every launch of the kernel classes above is bracketed by HIP
  * events on the handle's stream; read returns accumulated ms and launches */
