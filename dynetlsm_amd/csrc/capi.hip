@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "chain.hpp"
+#include "workspace.hpp"
 #include "device_common.hpp"
 #include "kernels_labels.hpp"
 #include "kernels_hdp.hpp"
@@ -148,6 +149,11 @@ struct SweepCall : Call {
         if (!(cond)) FAIL(h, DLSM_E_ARG, __VA_ARGS__);   \
     } while (0)
 
+// what DevArray::alloc reports (device_mem.hpp)
+int dlsm::mem_fail(dlsm_chain *h, hipError_t e, const char *call) {
+    FAIL(h, DLSM_E_HIP, "%s failed: %s", call, hipGetErrorString(e));
+}
+
 // dispatch on the compile-time latent dimension
 // (DLSM_DEV_ONLY_D2: development builds that instantiate n_features = 2 only - an eighth of the compile time
 // for A/B libraries under tmp_timing/; never the shipped library)
@@ -203,18 +209,26 @@ struct ProfScope {
     }
 };
 
-// a device allocation of one C-ABI call, freed when the call returns
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    template <typename T> T *as() const { return (T *)p; }
-};
-
+// A buffer of the handle that a captured iteration may hold the address of (partials, pipe, spec, xr, nctrl, cc_*,
+// lab_*, hdp_buf), grown to n elements: when it moves, the graph goes (the next dlsm_lsm_run captures again) and
+// `*stale`, the flag that says what the buffer holds is current, is cleared.
 template <typename T>
-int dev_alloc(dlsm_chain *h, T **p, size_t n) {
-    HIPCHK(h, hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    return DLSM_OK;
+int ensure_captured(dlsm_chain *h, DevArray<T> &buf, size_t n, bool *stale = nullptr) {
+    bool moved = false;
+    const int rc = buf.ensure(h, n, &moved);
+    if (moved) {
+        drop_graph(h);
+        if (stale) *stale = false;
+    }
+    return rc;
 }
+// ... a packed workspace, sized by its layout's run over a null base (workspace.hpp; every layout ends on 8 bytes)
+int ensure_workspace(dlsm_chain *h, DevArray<double> &buf, const Carve &sized) {
+    return ensure_captured(h, buf, sized.bytes() / sizeof(double));
+}
+
+// (a parameter the element type is not deduced from: a DevArray converts to it)
+template <typename T> struct as_given { using type = T; };
 
 // Host <-> device copies of the C-ABI, synchronous at return.  The caller's arrays are
 // pageable memory, for which the runtime's own staging is slow at these sizes
@@ -224,20 +238,20 @@ constexpr size_t STAGE_BYTES = 256 * 1024;
 constexpr size_t STAGE_D2H_MAX = 64 * 1024;    // beyond it the extra memcpy costs what it saves
 
 template <typename T>
-int h2d(dlsm_chain *h, T *dst, const T *src, size_t n) {
+int h2d(dlsm_chain *h, typename as_given<T *>::type dst, const T *src, size_t n) {
     const size_t bytes = n * sizeof(T);
     const void *from = src;
-    if (h->stage && bytes <= STAGE_BYTES) { memcpy(h->stage, src, bytes); from = h->stage; }
+    if (h->stage && bytes <= STAGE_BYTES) { memcpy(h->stage, src, bytes); from = h->stage.get(); }
     HIPCHK(h, hipMemcpyAsync(dst, from, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DLSM_OK;
 }
 
 template <typename T>
-int d2h(dlsm_chain *h, T *dst, const T *src, size_t n) {
+int d2h(dlsm_chain *h, T *dst, typename as_given<const T *>::type src, size_t n) {
     const size_t bytes = n * sizeof(T);
     const bool staged = h->stage && bytes <= STAGE_D2H_MAX;
-    HIPCHK(h, hipMemcpyAsync(staged ? h->stage : (void *)dst, src, bytes, hipMemcpyDeviceToHost,
+    HIPCHK(h, hipMemcpyAsync(staged ? (void *)h->stage.get() : (void *)dst, src, bytes, hipMemcpyDeviceToHost,
                              h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (staged) memcpy(dst, h->stage, bytes);
@@ -248,11 +262,11 @@ int d2h(dlsm_chain *h, T *dst, const T *src, size_t n) {
 // only enqueued (the synchronous d2h that ends the call, or the caller, waits for them).
 // `*off` = bytes of the buffer in use; a copy that does not fit goes the runtime's way.
 template <typename T>
-int h2d_enqueue(dlsm_chain *h, T *dst, const T *src, size_t n, size_t *off) {
+int h2d_enqueue(dlsm_chain *h, typename as_given<T *>::type dst, const T *src, size_t n, size_t *off) {
     const size_t bytes = n * sizeof(T);
     const void *from = src;
     if (h->stage && *off + bytes <= STAGE_BYTES) {
-        from = (char *)h->stage + *off;
+        from = h->stage + *off;
         memcpy((void *)from, src, bytes);
         *off += (bytes + 255) & ~(size_t)255;
     }
@@ -262,7 +276,7 @@ int h2d_enqueue(dlsm_chain *h, T *dst, const T *src, size_t n, size_t *off) {
 
 // int64 host array -> int32 device array; every value must lie in [lo, hi) (node indices
 // index device arrays: a bad one would be an out-of-bounds read in the kernels)
-int upload_i64_as_i32(dlsm_chain *h, int32_t **dst, const int64_t *src, size_t n,
+int upload_i64_as_i32(dlsm_chain *h, DevArray<int32_t> &dst, const int64_t *src, size_t n,
                       int64_t lo, int64_t hi, const char *what) {
     std::vector<int32_t> tmp(n);
     for (size_t i = 0; i < n; ++i) {
@@ -271,34 +285,20 @@ int upload_i64_as_i32(dlsm_chain *h, int32_t **dst, const int64_t *src, size_t n
                  (long long)src[i], (long long)lo, (long long)hi);
         tmp[i] = (int32_t)src[i];
     }
-    if (*dst) { hipFree(*dst); *dst = nullptr; }
-    int rc = dev_alloc(h, dst, n);
+    int rc = dst.alloc(h, n);
     if (rc) return rc;
-    return h2d(h, *dst, tmp.data(), n);
+    return h2d(h, dst, tmp.data(), n);
 }
 
-int ensure_partials(dlsm_chain *h, size_t n) {
-    if (h->partials_cap >= n) return DLSM_OK;
-    if (h->partials) hipFree(h->partials);
-    h->partials = nullptr; h->partials_cap = 0;
-    int rc = dev_alloc(h, &h->partials, n);
-    if (rc) return rc;
-    h->partials_cap = n;
-    return DLSM_OK;
-}
+int ensure_partials(dlsm_chain *h, size_t n) { return ensure_captured(h, h->partials, n); }
 
-// counts and transition matrices of the label update, sized for the current n_components
+// counts and transition matrices of the label update, sized for the current n_components (which may grow on a
+// live handle)
 int ensure_label_bufs(dlsm_chain *h) {
     const size_t nn = (size_t)h->T * h->K * h->K, nnk = (size_t)h->T * h->K;
-    if (h->lab_cap >= nn) return DLSM_OK;   // n_components may grow on a live handle
-    void *old[] = {h->lab_n, h->lab_nk, h->lab_w};
-    for (void *p : old) if (p) hipFree(p);
-    h->lab_n = h->lab_nk = nullptr; h->lab_w = nullptr; h->lab_cap = 0;
-    int rc = dev_alloc(h, &h->lab_n, nn); if (rc) return rc;
-    rc = dev_alloc(h, &h->lab_nk, nnk); if (rc) return rc;
-    rc = dev_alloc(h, &h->lab_w, nn); if (rc) return rc;
-    h->lab_cap = nn;
-    return DLSM_OK;
+    int rc = ensure_captured(h, h->lab_n, nn); if (rc) return rc;
+    rc = ensure_captured(h, h->lab_nk, nnk); if (rc) return rc;
+    return ensure_captured(h, h->lab_w, nn);
 }
 
 int ll_blocks(const dlsm_chain *h) {
@@ -325,41 +325,18 @@ int check_ready_loglik(dlsm_chain *h) {
 // set / resample clear the two flags).  alloc_only: buffers only (configure calls).
 static int ensure_cc_rows(dlsm_chain *h, hipStream_t q, bool alloc_only = false) {
     const size_t TN = (size_t)h->T * h->N;
-    if (h->nctrl_cap < TN * 2) {
-        if (h->nctrl) hipFree(h->nctrl);
-        h->nctrl = nullptr; h->nctrl_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->nctrl, TN * 2 * sizeof(int32_t)));
-        h->nctrl_cap = TN * 2;
-        h->nctrl_valid = false;
-    }
+    int rc = ensure_captured(h, h->nctrl, TN * 2, &h->nctrl_valid); if (rc) return rc;
     const int cap = std::max(1, h->Din + h->Dout + 2 * h->C);
     const int tw = cp_terms_width(cap);
-    const size_t n_terms = TN * tw;
-    if (h->cc_terms_cap < n_terms || h->cc_tw != tw) {
-        if (h->cc_terms_cap < n_terms) {
-            if (h->cc_terms) hipFree(h->cc_terms);
-            h->cc_terms = nullptr; h->cc_terms_cap = 0;
-            HIPCHK(h, hipMalloc((void **)&h->cc_terms, n_terms * sizeof(int32_t)));
-            h->cc_terms_cap = n_terms;
-        }
-        h->cc_tw = tw; h->cc_terms_valid = false;
-    }
+    rc = ensure_captured(h, h->cc_terms, TN * tw, &h->cc_terms_valid); if (rc) return rc;
+    if (h->cc_tw != tw) { h->cc_tw = tw; h->cc_terms_valid = false; }
     {   // the likelihood pass's walking order: entries of at most CC_ENT_TERMS out-terms (k_cc_order) + a count per slice
         const int emax = cc_order_entries_max(h->Dout, h->C);
-        if (h->cc_order_cap < TN * emax + (size_t)h->T || h->cc_emax != emax) {
-            if (h->cc_order) hipFree(h->cc_order);
-            h->cc_order = nullptr; h->cc_order_cap = 0;
-            HIPCHK(h, hipMalloc((void **)&h->cc_order, (TN * emax + (size_t)h->T) * sizeof(int32_t)));
-            h->cc_order_cap = TN * emax + (size_t)h->T; h->cc_emax = emax; h->cc_terms_valid = false;
-            h->cc_order_cnt = h->cc_order + TN * emax;
-        }
+        rc = ensure_captured(h, h->cc_order, TN * emax + (size_t)h->T, &h->cc_terms_valid); if (rc) return rc;
+        if (h->cc_emax != emax) { h->cc_emax = emax; h->cc_terms_valid = false; }
+        h->cc_order_cnt = h->cc_order + TN * emax;          // (the counts lie behind the entries of this width)
     }
-    if (h->cc_pos_cap < TN) {
-        if (h->cc_pos) hipFree(h->cc_pos);
-        h->cc_pos = nullptr; h->cc_pos_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->cc_pos, TN * sizeof(int32_t)));
-        h->cc_pos_cap = TN; h->cc_terms_valid = false;
-    }
+    rc = ensure_captured(h, h->cc_pos, TN, &h->cc_terms_valid); if (rc) return rc;
     if (alloc_only) return DLSM_OK;
     if (!h->nctrl_valid) {      // the control lists change only in set / resample
         hipLaunchKernelGGL(k_count_controls, dim3((unsigned)((TN + 255) / 256)), dim3(256),
@@ -385,14 +362,9 @@ static bool cc_prefetch_form(const dlsm_chain *h) {
 // its gather records (positions and both candidates' radii, one record per node)
 template <int DD>
 int ensure_xr(dlsm_chain *h) {
-    const size_t need = (size_t)h->T * h->N * llcc_record_width(DD);
-    if (h->xr_cap < need) {
-        if (h->xr) hipFree(h->xr);
-        h->xr = nullptr; h->xr_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->xr, need * sizeof(double)));
-        h->xr_cap = need;
-    }
-    return DLSM_OK;
+    Carve size;
+    xr_layout(size, h->T, h->N, llcc_record_width(DD));
+    return ensure_workspace(h, h->xr, size);
 }
 
 // The streaming case-control pass: as many workgroups per slice as stay resident together (occupancy query, once
@@ -564,14 +536,16 @@ int dlsm_create(int device, int T, int N, int D, int model, uint64_t seed,
     auto bail = [&](int rc) { g_err = h->err; dlsm_destroy(h); return rc; };
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
         { h->err = "hipStreamCreate failed"; return bail(DLSM_E_HIP); }
-    if (hipHostMalloc(&h->stage, STAGE_BYTES, hipHostMallocDefault) != hipSuccess)
-        h->stage = nullptr;                     // the copies then take the runtime's path
+    (void)h->stage.alloc(STAGE_BYTES);          // (without it the copies take the runtime's path)
     // the sticky error word of the in-kernel waits (the HDP-LPCM loop's two queues, the case-control sweep's
     // helper workgroups): host memory the device can store to, read by the host without a copy
     if (model == DLSM_DIRECTED_CASE_CONTROL && (!g_fix_err_host || g_fix_err_device != device)) {
         // (the first case-control chain of the process on this device; a second device re-points the word)
         int32_t *hostw = g_fix_err_host, *devw = nullptr;
-        if (!hostw && hipHostMalloc((void **)&hostw, 64, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) hostw = nullptr;
+        if (!hostw) {       // (the word lives as long as the process)
+            HostArray<int32_t> w;
+            if (w.alloc(16, HOST_MAPPED_PORTABLE) == hipSuccess) hostw = w.release();
+        }
         if (hostw) {
             if (!g_fix_err_host) memset(hostw, 0, 64);
             if (hipHostGetDevicePointer((void **)&devw, hostw, 0) == hipSuccess &&
@@ -581,28 +555,26 @@ int dlsm_create(int device, int T, int N, int D, int model, uint64_t seed,
         }
         (void)hipGetLastError();
     }
-    if (hipHostMalloc((void **)&h->fork_err_host, 64, hipHostMallocMapped) == hipSuccess) {
-        memset(h->fork_err_host, 0, 64);
-        if (hipHostGetDevicePointer((void **)&h->fork_err_dev, h->fork_err_host, 0) != hipSuccess) h->fork_err_dev = nullptr;
-    } else { h->fork_err_host = nullptr; (void)hipGetLastError(); }
+    if (h->fork_err.alloc(16, HOST_MAPPED) == hipSuccess) memset(h->fork_err, 0, 64);
+    else (void)hipGetLastError();
     const size_t TN = (size_t)T * N;
     int rc = 0;
-    rc |= dev_alloc(h, &h->X, TN * D);
-    rc |= dev_alloc(h, &h->intercept, 2);
-    rc |= dev_alloc(h, &h->radii, N);
-    rc |= dev_alloc(h, &h->radii_alt, N);
-    rc |= dev_alloc(h, &h->step, TN);
-    rc |= dev_alloc(h, &h->nacc, TN);
-    rc |= dev_alloc(h, &h->nsteps, TN);
-    rc |= dev_alloc(h, &h->until, TN);
-    rc |= dev_alloc(h, &h->dsmall, 128);
-    rc |= dev_alloc(h, &h->xref, TN * D);
-    rc |= dev_alloc(h, &h->lsm, 1);
-    rc |= dev_alloc(h, &h->z, TN);
-    rc |= dev_alloc(h, &h->hdp, 1);
+    rc |= h->X.alloc(h, TN * D);
+    rc |= h->intercept.alloc(h, 2);
+    rc |= h->radii.alloc(h, N);
+    rc |= h->radii_alt.alloc(h, N);
+    rc |= h->step.alloc(h, TN);
+    rc |= h->nacc.alloc(h, TN);
+    rc |= h->nsteps.alloc(h, TN);
+    rc |= h->until.alloc(h, TN);
+    rc |= h->dsmall.alloc(h, 128);
+    rc |= h->xref.alloc(h, TN * D);
+    rc |= h->lsm.alloc(h, 1);
+    rc |= h->z.alloc(h, TN);
+    rc |= h->hdp.alloc(h, 1);
     if (rc) return bail(DLSM_E_HIP);
-    if (hipHostMalloc((void **)&h->hsmall, 64 * sizeof(double)) != hipSuccess)
-        { h->err = "hipHostMalloc failed"; return bail(DLSM_E_HIP); }
+    if (h->hsmall.alloc(64) != hipSuccess)
+        { h->err = "pinned host allocation failed"; return bail(DLSM_E_HIP); }
     hipMemsetAsync(h->intercept, 0, 2 * sizeof(double), h->stream);
     hipMemsetAsync(h->lsm, 0, sizeof(LsmDeviceState), h->stream);
     hipMemsetAsync(h->hdp, 0, sizeof(HdpDeviceState), h->stream);
@@ -616,30 +588,17 @@ int dlsm_create(int device, int T, int N, int D, int model, uint64_t seed,
 void dlsm_destroy(dlsm_chain *h) {
     if (!h) return;
     hipSetDevice(h->device);
+    // nothing is freed under a running queue: both queues drain first, and the handle's arrays free themselves last
     if (h->stream) hipStreamSynchronize(h->stream);
+    if (h->fork_stream) hipStreamSynchronize(h->fork_stream);
     drain_profile(h);
-    void *ptrs[] = {h->ycm, h->ybits, h->ytbits, h->in_edges, h->out_edges, h->degree,
-                    h->ctrl_in, h->ctrl_out, h->X, h->intercept, h->radii,
-                    h->radii_alt, h->step, h->nacc, h->nsteps, h->until, h->mu,
-                    h->sigma, h->z, h->partials, h->dsmall, h->xref, h->lab_n,
-                    h->lab_nk, h->lab_w, h->spec, h->nctrl, h->stamps, h->lsm, h->trace_X, h->trace_ic,
-                    h->trace_logp, h->hops, h->hops_max, h->pipe, h->post_zt, h->post_cooc,
-                    h->trace_radii, h->hdp, h->hdp_buf, h->htr_mu, h->htr_sigma, h->htr_beta,
-                    h->htr_w, h->htr_lambda, h->htr_hyper, h->htr_z, h->xr, h->cc_terms, h->cc_pos, h->cc_order,
-                    h->miss_jobs, h->miss_cols, h->miss_slot, h->miss_psum, h->miss_ones, h->miss_nacc};
-    for (void *p : ptrs) if (p) hipFree(p);
-    if (h->hsmall) hipHostFree(h->hsmall);
     if (h->timer0) hipEventDestroy(h->timer0);
     if (h->timer1) hipEventDestroy(h->timer1);
-    if (h->fork_stream) { hipStreamSynchronize(h->fork_stream); hipStreamDestroy(h->fork_stream); }
     if (h->fork_ev) hipEventDestroy(h->fork_ev);
-    if (h->fork_flags) hipFree(h->fork_flags);
-    if (h->fork_err_host) hipHostFree(h->fork_err_host);
-    g_live_chains.fetch_sub(1);
-    if (h->graph_exec) hipGraphExecDestroy(h->graph_exec);
-    if (h->graph) hipGraphDestroy(h->graph);
+    drop_graph(h);
+    if (h->fork_stream) hipStreamDestroy(h->fork_stream);
     if (h->stream) hipStreamDestroy(h->stream);
-    if (h->stage) hipHostFree(h->stage);
+    g_live_chains.fetch_sub(1);
     delete h;
 }
 
@@ -659,21 +618,17 @@ int dlsm_upload_network(dlsm_chain *h, const double *Y) {
     HIPCHK(h, hipSetDevice(h->device));
     const size_t TN = (size_t)h->T * h->N;
     const size_t words = TN * h->W;
-    if (!h->ybits) { int rc = dev_alloc(h, &h->ybits, words); if (rc) return rc; }
+    if (!h->ybits) { int rc = h->ybits.alloc(h, words); if (rc) return rc; }
     if (h->model == DLSM_DIRECTED && !h->ytbits) {
-        int rc = dev_alloc(h, &h->ytbits, words); if (rc) return rc;
+        int rc = h->ytbits.alloc(h, words); if (rc) return rc;
     }
     // stage the float64 network one time slice at a time (bounded staging memory)
-    double *dY = nullptr;
-    int *dflag = nullptr;
+    DevArray<double> dY; DevArray<int> dflag;
     const size_t slice = (size_t)h->N * h->N;
-    HIPCHK(h, hipMalloc((void **)&dY, slice * sizeof(double)));
-    HIPCHK(h, hipMalloc((void **)&dflag, sizeof(int)));
+    if (dY.alloc(h, slice) || dflag.alloc(h, 1)) return DLSM_E_HIP;
     HIPCHK(h, hipMemsetAsync(dflag, 0, sizeof(int), h->stream));
     for (int t = 0; t < h->T; ++t) {
-        hipError_t e = hipMemcpyAsync(dY, Y + (size_t)t * slice, slice * sizeof(double),
-                                      hipMemcpyHostToDevice, h->stream);
-        if (e != hipSuccess) { hipFree(dY); hipFree(dflag); HIPCHK(h, e); }
+        HIPCHK(h, hipMemcpyAsync(dY, Y + (size_t)t * slice, slice * sizeof(double), hipMemcpyHostToDevice, h->stream));
         hipLaunchKernelGGL(k_pack_bits, dim3(h->N), dim3(256), 0, h->stream, dY, h->N,
                            h->W, 0, h->ybits + (size_t)t * h->N * h->W, dflag);
         if (h->model == DLSM_DIRECTED)
@@ -683,7 +638,6 @@ int dlsm_upload_network(dlsm_chain *h, const double *Y) {
     }
     int flag = 0;
     hipMemcpy(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost);
-    hipFree(dY); hipFree(dflag);
     HIPCHK(h, hipGetLastError());
     if (flag) FAIL(h, DLSM_E_DATA, "network has entries other than 0.0 / 1.0 (impute the -1 coded dyads once "
                                    "before the upload and list them with dlsm_set_missing to have them sampled)");
@@ -698,7 +652,7 @@ static int build_colmajor(dlsm_chain *h) {
     if (h->model != DLSM_UNDIRECTED) return DLSM_OK;
     const int Ncm = (h->N + 127) / 128 * 128;       // = ChainView::Ncm
     const size_t n = (size_t)h->T * (h->W / 2) * Ncm;
-    if (!h->ycm) { int rc = dev_alloc(h, &h->ycm, n); if (rc) return rc; }
+    if (!h->ycm) { int rc = h->ycm.alloc(h, n); if (rc) return rc; }
     hipLaunchKernelGGL(k_pack_colmajor, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ybits,
                        h->T, h->N, h->W, Ncm, h->ycm);
     HIPCHK(h, hipGetLastError());
@@ -739,9 +693,9 @@ int dlsm_set_network_packed(dlsm_chain *h, const uint32_t *buf, int64_t n_words)
     NEED(h, n_words == packed_words(h), "buffer must hold %lld words", (long long)packed_words(h));
     HIPCHK(h, hipSetDevice(h->device));
     const size_t one = (size_t)h->T * h->N * h->W;
-    if (!h->ybits) { int rc = dev_alloc(h, &h->ybits, one); if (rc) return rc; }
+    if (!h->ybits) { int rc = h->ybits.alloc(h, one); if (rc) return rc; }
     if (h->model == DLSM_DIRECTED && !h->ytbits) {
-        int rc = dev_alloc(h, &h->ytbits, one); if (rc) return rc;
+        int rc = h->ytbits.alloc(h, one); if (rc) return rc;
     }
     HIPCHK(h, hipMemcpyAsync(h->ybits, buf, one * sizeof(uint32_t), hipMemcpyDefault, h->stream));
     if (h->model == DLSM_DIRECTED)
@@ -782,11 +736,11 @@ int dlsm_upload_edges(dlsm_chain *h, const int64_t *in_edges, int Din,
     // a failed re-upload must not leave new lists behind old strides: the chain has no edges
     // until all three arrays are in
     h->have_edges = false;
-    int rc = upload_i64_as_i32(h, &h->in_edges, in_edges, TN * Din, 0, h->N, "in_edges");
+    int rc = upload_i64_as_i32(h, h->in_edges, in_edges, TN * Din, 0, h->N, "in_edges");
     if (rc) return rc;
-    rc = upload_i64_as_i32(h, &h->out_edges, out_edges, TN * Dout, 0, h->N, "out_edges");
+    rc = upload_i64_as_i32(h, h->out_edges, out_edges, TN * Dout, 0, h->N, "out_edges");
     if (rc) return rc;
-    rc = upload_i64_as_i32(h, &h->degree, degree, TN * 2, 0, (int64_t)h->N, "degree");
+    rc = upload_i64_as_i32(h, h->degree, degree, TN * 2, 0, (int64_t)h->N, "degree");
     if (rc) return rc;
     h->Din = Din; h->Dout = Dout;
     h->have_edges = true;
@@ -803,9 +757,9 @@ int dlsm_set_controls(dlsm_chain *h, const int64_t *ctrl_in, const int64_t *ctrl
     const size_t TN = (size_t)h->T * h->N;
     h->have_controls = false;                       // (as dlsm_upload_edges)
     h->nctrl_valid = false; h->cc_terms_valid = false;
-    int rc = upload_i64_as_i32(h, &h->ctrl_in, ctrl_in, TN * C, -1, h->N, "control_nodes_in");
+    int rc = upload_i64_as_i32(h, h->ctrl_in, ctrl_in, TN * C, -1, h->N, "control_nodes_in");
     if (rc) return rc;                              // -1 = padding
-    rc = upload_i64_as_i32(h, &h->ctrl_out, ctrl_out, TN * C, -1, h->N, "control_nodes_out");
+    rc = upload_i64_as_i32(h, h->ctrl_out, ctrl_out, TN * C, -1, h->N, "control_nodes_out");
     if (rc) return rc;
     h->C = C;
     h->have_controls = true;
@@ -835,11 +789,8 @@ int dlsm_resample_controls(dlsm_chain *h, uint32_t iter, int n_control) {
     HIPCHK(h, hipSetDevice(h->device));
     const size_t TN = (size_t)h->T * h->N;
     if (h->C != n_control || !h->ctrl_in) {
-        if (h->ctrl_in) hipFree(h->ctrl_in);
-        if (h->ctrl_out) hipFree(h->ctrl_out);
-        h->ctrl_in = h->ctrl_out = nullptr;
-        int rc = dev_alloc(h, &h->ctrl_in, TN * n_control); if (rc) return rc;
-        rc = dev_alloc(h, &h->ctrl_out, TN * n_control); if (rc) return rc;
+        h->ctrl_out.reset();
+        if (h->ctrl_in.alloc(h, TN * n_control) || h->ctrl_out.alloc(h, TN * n_control)) return DLSM_E_HIP;
         h->C = n_control;
     }
     ChainView v = h->view();
@@ -960,11 +911,8 @@ int dlsm_set_prior_mixture(dlsm_chain *h, const double *mu, const double *sigma,
     for (size_t i = 0; z && i < TN; ++i)
         if (z[i] < 0 || z[i] >= K) FAIL(h, DLSM_E_DATA, "label out of range at %zu", i);
     if (h->K != K) {
-        if (h->mu) hipFree(h->mu);
-        if (h->sigma) hipFree(h->sigma);
-        h->mu = h->sigma = nullptr;
-        int rc = dev_alloc(h, &h->mu, (size_t)K * h->D); if (rc) return rc;
-        rc = dev_alloc(h, &h->sigma, K); if (rc) return rc;
+        h->sigma.reset();
+        if (h->mu.alloc(h, (size_t)K * h->D) || h->sigma.alloc(h, K)) return DLSM_E_HIP;
         h->K = K;
     }
     size_t staged = 0;                          // one synchronisation for the whole upload
@@ -1122,20 +1070,10 @@ static int launch_sweep_spec(dlsm_chain *h, const SweepCall &sc, IterRef iter, i
     int parts = (1024 + nsl_max * SP_BMAX - 1) / (nsl_max * SP_BMAX);
     parts = std::max(1, std::min(parts, 8));
     if (h->model == DLSM_DIRECTED_CASE_CONTROL) parts = 1;
-    auto even2 = [](size_t n) { return (n + 1) / 2 * 2; };
-    const size_t n_full0 = even2((size_t)nsl_max * B * parts);
-    const size_t n_prop = even2((size_t)nsl_max * N * (DD + 2));
-    const size_t n_ht = (size_t)nsl_max * B * B;
-    const size_t need = (n_full0 + n_prop + n_ht + 2) * sizeof(double);
-    if (h->spec_cap < need) {
-        if (h->spec) hipFree(h->spec);
-        h->spec = nullptr; h->spec_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->spec, need));
-        h->spec_cap = need;
-    }
     SpecBuf sb;
-    sb.full0 = h->spec; sb.prop = sb.full0 + n_full0; sb.Ht = sb.prop + n_prop;
-    sb.consts = sb.Ht + n_ht;
+    Carve size; spec_layout(size, sb, nsl_max, N, DD, B, parts);
+    { int rc = ensure_workspace(h, h->spec, size); if (rc) return rc; }
+    Carve at(h->spec); spec_layout(at, sb, nsl_max, N, DD, B, parts);
     sb.B = B; sb.parts = parts; sb.s0 = 0; sb.per = (N + parts - 1) / parts;
     sb.stamps = nullptr;
     ChainView v = h->view();
@@ -1155,7 +1093,7 @@ static int launch_sweep_spec(dlsm_chain *h, const SweepCall &sc, IterRef iter, i
             SpecBuf sg = sb;
             const size_t nblk = (size_t)parts * nsb * nsl;
             if (h->profiling && h->stamps && h->model != DLSM_DIRECTED_CASE_CONTROL &&
-                h->stamps_used + nblk <= h->stamps_cap) {
+                h->stamps_used + nblk <= h->stamps.size() / 2) {
                 sg.stamps = h->stamps + 2 * h->stamps_used;
                 h->stamp_launches.emplace_back(h->stamps_used, nblk);
                 h->stamps_used += nblk;
@@ -1212,11 +1150,11 @@ static int check_pipe_err(dlsm_chain *h) {
         FAIL(h, DLSM_E_HIP, "case-control sweep: a resolver's fixed point did not settle inside its spin bound "
              "(word %#x) - the state of this process's case-control chains is undefined; set it again", e);
     }
-    if (h->fork_err_host) {
+    if (h->fork_err.get()) {
         // (behind a synchronisation of the handle's stream: the word is host memory the device stores to)
-        const int32_t e = *(volatile int32_t *)h->fork_err_host;
+        const int32_t e = *(volatile int32_t *)h->fork_err.get();
         if (e != 0) {
-            *(volatile int32_t *)h->fork_err_host = 0;
+            *(volatile int32_t *)h->fork_err.get() = 0;
             if (e & PP_ERR_XSERVE)
                 FAIL(h, DLSM_E_HIP, "pipelined sweep: a resolver ran out of its poll budget waiting for a cross product "
                      "from the launch's evaluators (word %#x) - the chain's state is undefined; set the state again "
@@ -1251,26 +1189,11 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
         parts = CC_PARTS;
         ne_wg = std::min(ne_wg, (T * PP_B * CC_PARTS + PP_WAVES - 1) / PP_WAVES);
     }
-    auto even2 = [](size_t n) { return (n + 1) / 2 * 2; };
-    const size_t n_prop = even2((size_t)T * N * (2 * DD + 2));
-    // (PipeBuf: two batch slots of everything produced per batch)
-    const size_t n_full0 = (size_t)2 * T * PP_B * parts * 2;
-    const size_t n_h = pipe_h_doubles(T);
-    const size_t n_acc = even2(((size_t)T * 2 * PP_ACC + 1) / 2);   // int32 pairs
-    const size_t n_xp = (size_t)T * PP_B;
-    const size_t need = (n_prop + n_full0 + n_h + n_acc + 2 + n_xp) * sizeof(double);
-    if (h->pipe_cap < need) {
-        if (h->pipe) hipFree(h->pipe);
-        h->pipe = nullptr; h->pipe_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->pipe, need));
-        h->pipe_cap = need;
-    }
     PipeBuf pb{};
-    pb.prop = h->pipe; pb.full0 = pb.prop + n_prop; pb.H = pb.full0 + n_full0;
-    pb.acc = (int32_t *)(pb.H + n_h);
-    pb.consts = pb.H + n_h + n_acc;
-    pb.xprod = pb.consts + 2;
-    pb.lsm_draw = sc.draw_intercept ? h->lsm : nullptr;
+    Carve size; pipe_layout(size, pb, T, N, DD, PP_B, parts, pipe_h_doubles(T), PP_ACC);
+    { int rc = ensure_workspace(h, h->pipe, size); if (rc) return rc; }
+    Carve at(h->pipe); pipe_layout(at, pb, T, N, DD, PP_B, parts, pipe_h_doubles(T), PP_ACC);
+    pb.lsm_draw = sc.draw_intercept ? h->lsm.get() : nullptr;
     pb.parts = parts; pb.nbat = nbat;
     pb.per = ((N + parts - 1) / parts + 63) / 64 * 64;      // parts start on a 64-neighbour boundary
     pb.nctrl = h->nctrl;
@@ -1283,7 +1206,7 @@ static int launch_sweep_pipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
                   (long)parts * T * PP_B <= (long)ne_wg * PP_WAVES && kn.pipe_lds;
     // the resolvers' cross products by the evaluators (pipe_xserve_*): one wavefront in xstride takes a row.  A
     // resolver waits INSIDE the launch for wavefronts that wait for nothing - they only have to start
-    pb.err = h->fork_err_dev;
+    pb.err = h->fork_err.dev();
     pb.budget = kn.pipe_xbudget;
     // (one chain on the device: with several, a resolver's wait for evaluator workgroups that other chains' launches
     // keep off the CUs costs more than the cross block - four chains: 6100 it/s served, 6970 not; DLSM_PIPE_XSERVE=2
@@ -1393,24 +1316,9 @@ static int launch_sweep_ccpipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
     const int N = h->N, T = h->T;
     const int nbat = (N + CP_B - 1) / CP_B;
     const int cap = std::max(1, h->Din + h->Dout + 2 * h->C);   // either list may hold every term
-    auto even2 = [](size_t n) { return (n + 1) / 2 * 2; };
-    const size_t n_prop = even2((size_t)T * N * (2 * DD + 2));
-    const size_t n_tot = (size_t)2 * T * CP_B;
-    const size_t n_ent = (size_t)2 * T * cap * CP_B;
-    const size_t n_cnt = (size_t)2 * T * CP_B * 2;
-    const size_t n_rec = (size_t)T * N * cp_record_width(DD);
-    // doubles: prop | tot | xval | oval | consts(2) | cur | snap | xsum ; int32: xidx | oidx | cnt ;
-    // uint64: accmask
-    const size_t n_xsum = (size_t)T * CP_B;
-    const size_t need = (n_prop + n_tot + 2 * n_ent + 2 + 2 * n_rec + n_xsum) * sizeof(double) +
-                        even2(2 * n_ent + n_cnt) * sizeof(int32_t) +
-                        (size_t)T * CP_WAVES * sizeof(unsigned long long);
-    if (h->pipe_cap < need) {
-        if (h->pipe) hipFree(h->pipe);
-        h->pipe = nullptr; h->pipe_cap = 0;
-        HIPCHK(h, hipMalloc((void **)&h->pipe, need));
-        h->pipe_cap = need;
-    }
+    CcPipeBuf pb;
+    Carve size; ccpipe_layout(size, pb, T, N, DD, CP_B, cap, cp_record_width(DD), CP_WAVES);
+    { int rc = ensure_workspace(h, h->pipe, size); if (rc) return rc; }
     // (the gathers address records and proposals as 32-bit lane offsets from per-slice bases: umul24 of the node
     // and a snapshot offset of T N records - round-5 advice)
     if (N >= (1 << 24) || (double)(T + 1) * N * cp_record_width(DD) * sizeof(double) >= 4294967296.0)
@@ -1420,23 +1328,18 @@ static int launch_sweep_ccpipe(dlsm_chain *h, SweepCall &sc, IterRef iter) {
     { int rc_ = ensure_cc_rows(h, q, sc.alloc_only); if (rc_) return rc_; }
     const int tw = h->cc_tw;
     if (sc.alloc_only) return DLSM_OK;
-    CcPipeBuf pb;
-    pb.prop = h->pipe; pb.tot = pb.prop + n_prop; pb.xval = pb.tot + n_tot; pb.oval = pb.xval + n_ent;
-    double *consts = pb.oval + n_ent;
-    pb.cur = consts + 2; pb.snap = pb.cur + n_rec;
-    pb.xsum = pb.snap + n_rec;
-    pb.xidx = (int32_t *)(pb.xsum + n_xsum); pb.oidx = pb.xidx + n_ent; pb.cnt = pb.oidx + n_ent;
-    pb.accmask = (unsigned long long *)(pb.xidx + even2(2 * n_ent + n_cnt));
+    Carve at(h->pipe);
+    double *consts = ccpipe_layout(at, pb, T, N, DD, CP_B, cap, cp_record_width(DD), CP_WAVES);
     // a helper workgroup per resolver (kernels_ccpipe.hpp, ccpipe_cross_helper) when the launch still fits the
     // device in one wave of workgroups - a resolver waits for its helper INSIDE the launch, so both must be
     // resident; DLSM_CC_HELPERS=0 keeps the resolvers on their own
     // (one chain on the device - as hdp_fork_arm and the pipelined sweep's served cross products decide: with several
     // chains' launches on the CUs a helper may not be resident when its resolver starts to poll, and a slow but
     // correct run would end in the sticky error; DLSM_CC_HELPERS=2 forces the role, 0 switches it off)
-    pb.helpers = alone_or_forced(sc.knobs.cc_helpers, 0, 2) && h->n_cu >= 4 * T && h->fork_err_dev != nullptr;
+    pb.helpers = alone_or_forced(sc.knobs.cc_helpers, 0, 2) && h->n_cu >= 4 * T && h->fork_err.dev() != nullptr;
     // polls of a resolver's wait for its helper before the sticky error word is set (DLSM_CC_HELPER_BUDGET)
     pb.budget = sc.knobs.cc_helper_budget;
-    pb.err = h->fork_err_dev;
+    pb.err = h->fork_err.dev();
     pb.nctrl = h->nctrl; pb.cap = cap; pb.nbat = nbat;
     pb.terms = h->cc_terms; pb.tw = tw;
     PipeBuf pp{};                   // the proposal kernel's view: proposals + its two constants
@@ -1827,15 +1730,13 @@ int dlsm_trace_alloc(dlsm_chain *h, int n_total, double logp0) {
     NEED(h, h->have_X, "latent positions not set");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t row = (size_t)h->T * h->N * h->D;
-    void *old[] = {h->trace_X, h->trace_ic, h->trace_logp, h->trace_radii};
-    for (void *p : old) if (p) hipFree(p);
-    h->trace_X = h->trace_ic = h->trace_logp = h->trace_radii = nullptr;
-    int rc = dev_alloc(h, &h->trace_X, row * n_total); if (rc) return rc;
-    rc = dev_alloc(h, &h->trace_ic, (size_t)2 * n_total); if (rc) return rc;
-    rc = dev_alloc(h, &h->trace_logp, n_total); if (rc) return rc;
+    // (the old trace goes first: the new one may need its room)
+    h->trace_X.reset(); h->trace_ic.reset(); h->trace_logp.reset(); h->trace_radii.reset();
+    if (h->trace_X.alloc(h, row * n_total) || h->trace_ic.alloc(h, (size_t)2 * n_total) ||
+        h->trace_logp.alloc(h, n_total)) return DLSM_E_HIP;
     if (h->model != DLSM_UNDIRECTED) {
         NEED(h, h->have_radii, "radii not set");
-        rc = dev_alloc(h, &h->trace_radii, (size_t)h->N * n_total); if (rc) return rc;
+        if (h->trace_radii.alloc(h, (size_t)h->N * n_total)) return DLSM_E_HIP;
         HIPCHK(h, hipMemcpyAsync(h->trace_radii, h->radii, h->N * sizeof(double),
                                  hipMemcpyDeviceToDevice, h->stream));
     }
@@ -1887,7 +1788,7 @@ static int enqueue_directed_steps(dlsm_chain *h, const Call &c, IterRef ir, cons
     double *ll2 = h->dsmall + 16;
     double *prec = h->partials + (size_t)ll_blocks(h) * 4;
     double *rrec = prec + n_post, *rrec2 = rrec + nblk;
-    double *xr = pf ? h->xr : nullptr;
+    double *xr = pf ? h->xr.get() : nullptr;
     const long rows = (long)h->T * h->N;
     const int nbp = (int)std::min<long>(PS_BLOCKS, (rows + PS2_THREADS - 1) / PS2_THREADS);
     {
@@ -2061,7 +1962,7 @@ int dlsm_lsm_run(dlsm_chain *h, int first, int count, int procrustes_ref) {
             }
         }
         if (h->graph_exec) {
-            uint32_t *hp = (uint32_t *)h->hsmall;
+            uint32_t *hp = (uint32_t *)h->hsmall.get();
             hp[0] = (uint32_t)(first - 1);
             HIPCHK(h, hipMemcpyAsync(&h->lsm->iter, hp, sizeof(uint32_t), hipMemcpyHostToDevice,
                                      h->stream));
@@ -2161,11 +2062,8 @@ int dlsm_profile_enable(dlsm_chain *h, int on) {
         // in-kernel wall-clock stamps of the sweep's eval launches: [start, end] per
         // workgroup (plain stores, no atomics: nothing contends)
         const size_t cap = (size_t)2 << 20;                     // pairs (32 MB)
-        if (!h->stamps) {
-            HIPCHK(h, hipMalloc((void **)&h->stamps, cap * 2 * sizeof(unsigned long long)));
-            h->stamps_cap = cap;
-        }
-        HIPCHK(h, hipMemset(h->stamps, 0, h->stamps_cap * 2 * sizeof(unsigned long long)));
+        { int rc = h->stamps.ensure(h, cap * 2); if (rc) return rc; }
+        HIPCHK(h, hipMemset(h->stamps, 0, h->stamps.size() * sizeof(unsigned long long)));
         h->stamps_used = 0;
         h->stamp_launches.clear();
     }

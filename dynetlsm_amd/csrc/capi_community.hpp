@@ -1,4 +1,4 @@
-// C-ABI of the community structure of stored labellings (kernels_community.hpp); the error macros, DevBuf and
+// C-ABI of the community structure of stored labellings (kernels_community.hpp); the error macros, DevArray and
 // check_packed_network (capi_samples.hpp) are capi.hip's.  The reference has modularity(Y, z) alone
 // (network_statistics.py:31-61), for one labelling on the host.
 #pragma once
@@ -88,35 +88,31 @@ int dlsm_community_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_
     if (!batch && blocks) chunk = std::max<size_t>(1, std::min(chunk, ((size_t)64 << 20) / (n_bl * sizeof(int64_t))));
     chunk = std::min<size_t>(chunk, S);
     const size_t n_net = per * W;
-    DevBuf stage, z8, d_bits, d_mask, d_indeg, d_cl, d_nw, d_sw, d_mv, d_bl;
-    HIPCHK(h, hipMalloc(&stage.p, chunk * per * sizeof(int64_t)));
-    HIPCHK(h, hipMalloc(&z8.p, chunk * per));
-    HIPCHK(h, hipMalloc(&d_bits.p, n_net * sizeof(uint32_t)));
-    if (mask) HIPCHK(h, hipMalloc(&d_mask.p, n_net * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&d_indeg.p, per * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&d_cl.p, chunk * n_cl * sizeof(cm_count_t)));
-    HIPCHK(h, hipMalloc(&d_nw.p, per * sizeof(cm_count_t)));
+    DevArray<int64_t> stage; DevArray<uint8_t> z8;
+    DevArray<uint32_t> d_bits, d_mask, d_indeg; DevArray<cm_count_t> d_cl, d_nw, d_sw, d_mv, d_bl;
+    if (stage.alloc(h, chunk * per) || z8.alloc(h, chunk * per) || d_bits.alloc(h, n_net) ||
+        (mask && d_mask.alloc(h, n_net)) || d_indeg.alloc(h, per) || d_cl.alloc(h, chunk * n_cl) ||
+        d_nw.alloc(h, per)) return DLSM_E_HIP;
     if (U) {
-        HIPCHK(h, hipMalloc(&d_sw.p, (size_t)U * N * sizeof(cm_count_t)));
-        HIPCHK(h, hipMalloc(&d_mv.p, chunk * U * sizeof(cm_count_t)));
-        HIPCHK(h, hipMemsetAsync(d_sw.p, 0, (size_t)U * N * sizeof(cm_count_t), h->stream));
+        if (d_sw.alloc(h, (size_t)U * N) || d_mv.alloc(h, chunk * U)) return DLSM_E_HIP;
+        HIPCHK(h, hipMemsetAsync(d_sw, 0, (size_t)U * N * sizeof(cm_count_t), h->stream));
     }
-    if (blocks) HIPCHK(h, hipMalloc(&d_bl.p, chunk * n_bl * sizeof(cm_count_t)));
-    HIPCHK(h, hipMemcpyAsync(d_bits.p, bits, n_net * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    if (mask) HIPCHK(h, hipMemcpyAsync(d_mask.p, eff.data(), n_net * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_indeg.p, indeg.data(), per * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(d_nw.p, 0, per * sizeof(cm_count_t), h->stream));
+    if (blocks) { if (int rc = d_bl.alloc(h, chunk * n_bl)) return rc; }
+    HIPCHK(h, hipMemcpyAsync(d_bits, bits, n_net * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if (mask) HIPCHK(h, hipMemcpyAsync(d_mask, eff.data(), n_net * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_indeg, indeg.data(), per * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_nw, 0, per * sizeof(cm_count_t), h->stream));
     CommArgs a;
-    a.z8 = z8.as<uint8_t>(); a.bits = d_bits.as<uint32_t>(); a.mask = d_mask.as<uint32_t>();
-    a.indeg = d_indeg.as<uint32_t>(); a.T = T; a.N = N; a.W = W; a.K = K; a.lpr = lpr;
-    a.clusters = d_cl.as<cm_count_t>(); a.node_within = d_nw.as<cm_count_t>(); a.blocks = d_bl.as<cm_count_t>();
+    a.z8 = z8; a.bits = d_bits; a.mask = d_mask;
+    a.indeg = d_indeg; a.T = T; a.N = N; a.W = W; a.K = K; a.lpr = lpr;
+    a.clusters = d_cl; a.node_within = d_nw; a.blocks = d_bl;
     for (size_t s0 = 0; s0 < (size_t)S; s0 += chunk) {
         const int ns = (int)std::min(chunk, (size_t)S - s0);
         const size_t n_lab = (size_t)ns * per;
-        HIPCHK(h, hipMemcpyAsync(stage.p, zs + s0 * per, n_lab * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemsetAsync(d_cl.p, 0, (size_t)ns * n_cl * sizeof(cm_count_t), h->stream));
-        if (U) HIPCHK(h, hipMemsetAsync(d_mv.p, 0, (size_t)ns * U * sizeof(cm_count_t), h->stream));
-        if (blocks) HIPCHK(h, hipMemsetAsync(d_bl.p, 0, (size_t)ns * n_bl * sizeof(cm_count_t), h->stream));
+        HIPCHK(h, hipMemcpyAsync(stage, zs + s0 * per, n_lab * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(d_cl, 0, (size_t)ns * n_cl * sizeof(cm_count_t), h->stream));
+        if (U) HIPCHK(h, hipMemsetAsync(d_mv, 0, (size_t)ns * U * sizeof(cm_count_t), h->stream));
+        if (blocks) HIPCHK(h, hipMemsetAsync(d_bl, 0, (size_t)ns * n_bl * sizeof(cm_count_t), h->stream));
         // (some 8 workgroups per CU: sample groups first - a group re-stages N bytes per sample, a row chunk
         // flushes a cluster table per sample)
         const int target = 8 * std::max(h->n_cu, 1);
@@ -128,26 +124,26 @@ int dlsm_community_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_
         {
             ProfScope ps(h, DLSM_K_LABELS);
             const unsigned nb = (unsigned)std::min<size_t>(4096, (n_lab + 255) / 256);
-            hipLaunchKernelGGL(k_comm_pack_labels, dim3(nb), dim3(256), 0, h->stream, stage.as<int64_t>(), n_lab,
-                               z8.as<uint8_t>());
+            hipLaunchKernelGGL(k_comm_pack_labels, dim3(nb), dim3(256), 0, h->stream, stage, n_lab,
+                               z8);
             if (blocks) hipLaunchKernelGGL(k_comm_rows<true>, grid, dim3(CM_NT), lds, h->stream, a);
             else hipLaunchKernelGGL(k_comm_rows<false>, grid, dim3(CM_NT), lds, h->stream, a);
             if (U)
                 hipLaunchKernelGGL(k_comm_switch, dim3((unsigned)((N + 255) / 256), (unsigned)U), dim3(256), 0,
-                                   h->stream, z8.as<uint8_t>(), ns, T, N, d_sw.as<cm_count_t>(),
-                                   d_mv.as<cm_count_t>());
+                                   h->stream, z8, ns, T, N, d_sw,
+                                   d_mv);
         }
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(clusters + s0 * n_cl, d_cl.p, (size_t)ns * n_cl * sizeof(int64_t),
+        HIPCHK(h, hipMemcpyAsync(clusters + s0 * n_cl, d_cl, (size_t)ns * n_cl * sizeof(int64_t),
                                  hipMemcpyDeviceToHost, h->stream));
-        if (U) HIPCHK(h, hipMemcpyAsync(moved + s0 * U, d_mv.p, (size_t)ns * U * sizeof(int64_t),
+        if (U) HIPCHK(h, hipMemcpyAsync(moved + s0 * U, d_mv, (size_t)ns * U * sizeof(int64_t),
                                         hipMemcpyDeviceToHost, h->stream));
-        if (blocks) HIPCHK(h, hipMemcpyAsync(blocks + s0 * n_bl, d_bl.p, (size_t)ns * n_bl * sizeof(int64_t),
+        if (blocks) HIPCHK(h, hipMemcpyAsync(blocks + s0 * n_bl, d_bl, (size_t)ns * n_bl * sizeof(int64_t),
                                              hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));         // the staging buffers are reused
     }
-    HIPCHK(h, hipMemcpyAsync(node_within, d_nw.p, per * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    if (U) HIPCHK(h, hipMemcpyAsync(node_switch, d_sw.p, (size_t)U * N * sizeof(int64_t), hipMemcpyDeviceToHost,
+    HIPCHK(h, hipMemcpyAsync(node_within, d_nw, per * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    if (U) HIPCHK(h, hipMemcpyAsync(node_switch, d_sw, (size_t)U * N * sizeof(int64_t), hipMemcpyDeviceToHost,
                                     h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DLSM_OK;

@@ -56,20 +56,15 @@ int dlsm_forecast_paths(dlsm_chain *h, const double *X0, const double *intercept
     nb = std::min(nb, S);
     nb = std::min(nb, 65535);                              // the draw grid's y extent
     const size_t ND = (size_t)N * D;
-    DevBuf bX, bB, bR, bZ, bW, bM, bSg, bL, bP, bLab, bSum;
-    HIPCHK(h, hipMalloc(&bX.p, (size_t)nb * ND * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bB.p, (size_t)nb * 2 * sizeof(double)));
-    if (directed) HIPCHK(h, hipMalloc(&bR.p, (size_t)nb * N * sizeof(double)));
+    DevArray<double> bX, bB, bR, bW, bM, bSg, bL, bP, bSum; DevArray<int32_t> bZ, bLab;
+    if (bX.alloc(h, (size_t)nb * ND) || bB.alloc(h, (size_t)nb * 2) ||
+        (directed && bR.alloc(h, (size_t)nb * N))) return DLSM_E_HIP;
     if (mixture) {
-        HIPCHK(h, hipMalloc(&bZ.p, (size_t)nb * N * sizeof(int32_t)));
-        HIPCHK(h, hipMalloc(&bW.p, (size_t)nb * K * K * sizeof(double)));
-        HIPCHK(h, hipMalloc(&bM.p, (size_t)nb * K * D * sizeof(double)));
-        HIPCHK(h, hipMalloc(&bSg.p, (size_t)nb * K * sizeof(double)));
-        HIPCHK(h, hipMalloc(&bL.p, (size_t)nb * sizeof(double)));
-        HIPCHK(h, hipMalloc(&bLab.p, (size_t)H * nb * N * sizeof(int32_t)));
+        if (bZ.alloc(h, (size_t)nb * N) || bW.alloc(h, (size_t)nb * K * K) || bM.alloc(h, (size_t)nb * K * D) ||
+            bSg.alloc(h, (size_t)nb * K) || bL.alloc(h, (size_t)nb) ||
+            bLab.alloc(h, (size_t)H * nb * N)) return DLSM_E_HIP;
     }
-    HIPCHK(h, hipMalloc(&bP.p, (size_t)H * nb * ND * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bSum.p, (size_t)H * N * N * sizeof(double)));
+    if (bP.alloc(h, (size_t)H * nb * ND) || bSum.alloc(h, (size_t)H * N * N)) return DLSM_E_HIP;
     // the draws come back horizon-major; the caller's arrays are sample-major
     std::vector<double> hostP;
     std::vector<int32_t> hostL;
@@ -78,44 +73,44 @@ int dlsm_forecast_paths(dlsm_chain *h, const double *X0, const double *intercept
     const int nt = (N + FC_TILE - 1) / FC_TILE;
     for (int s0 = 0; s0 < S; s0 += nb) {
         const int n = std::min(nb, S - s0);
-        HIPCHK(h, hipMemcpyAsync(bX.p, X0 + (size_t)s0 * ND, (size_t)n * ND * sizeof(double), hipMemcpyHostToDevice,
+        HIPCHK(h, hipMemcpyAsync(bX, X0 + (size_t)s0 * ND, (size_t)n * ND * sizeof(double), hipMemcpyHostToDevice,
                                  h->stream));
-        HIPCHK(h, hipMemcpyAsync(bB.p, intercepts + 2 * (size_t)s0, (size_t)n * 2 * sizeof(double),
+        HIPCHK(h, hipMemcpyAsync(bB, intercepts + 2 * (size_t)s0, (size_t)n * 2 * sizeof(double),
                                  hipMemcpyHostToDevice, h->stream));
         if (directed)
-            HIPCHK(h, hipMemcpyAsync(bR.p, radii + (size_t)s0 * N, (size_t)n * N * sizeof(double),
+            HIPCHK(h, hipMemcpyAsync(bR, radii + (size_t)s0 * N, (size_t)n * N * sizeof(double),
                                      hipMemcpyHostToDevice, h->stream));
         if (mixture) {
-            HIPCHK(h, hipMemcpyAsync(bZ.p, z0 + (size_t)s0 * N, (size_t)n * N * sizeof(int32_t),
+            HIPCHK(h, hipMemcpyAsync(bZ, z0 + (size_t)s0 * N, (size_t)n * N * sizeof(int32_t),
                                      hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(bW.p, trans + (size_t)s0 * K * K, (size_t)n * K * K * sizeof(double),
+            HIPCHK(h, hipMemcpyAsync(bW, trans + (size_t)s0 * K * K, (size_t)n * K * K * sizeof(double),
                                      hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(bM.p, mu + (size_t)s0 * K * D, (size_t)n * K * D * sizeof(double),
+            HIPCHK(h, hipMemcpyAsync(bM, mu + (size_t)s0 * K * D, (size_t)n * K * D * sizeof(double),
                                      hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(bSg.p, sigma + (size_t)s0 * K, (size_t)n * K * sizeof(double),
+            HIPCHK(h, hipMemcpyAsync(bSg, sigma + (size_t)s0 * K, (size_t)n * K * sizeof(double),
                                      hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(bL.p, lmbda + s0, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
+            HIPCHK(h, hipMemcpyAsync(bL, lmbda + s0, (size_t)n * sizeof(double), hipMemcpyHostToDevice,
                                      h->stream));
         }
         {
             ProfScope ps(h, DLSM_K_LOGLIK);
             DISPATCH_D(h, D, hipLaunchKernelGGL((k_forecast_paths_draw<DD>), dim3((unsigned)((N + 255) / 256), (unsigned)n),
-                                                dim3(256), 0, h->stream, bX.as<double>(),
-                                                mixture ? bZ.as<int32_t>() : nullptr, bW.as<double>(),
-                                                bM.as<double>(), bSg.as<double>(), bL.as<double>(), K, sigma_sq, H,
-                                                N, seed, first_index + (uint32_t)s0, bP.as<double>(),
-                                                bLab.as<int32_t>()));
+                                                dim3(256), 0, h->stream, bX,
+                                                mixture ? bZ.get() : nullptr, bW,
+                                                bM, bSg, bL, K, sigma_sq, H,
+                                                N, seed, first_index + (uint32_t)s0, bP,
+                                                bLab));
             HIPCHK(h, hipGetLastError());
             DISPATCH_D(h, D, LAUNCH_DIR(directed, k_forecast_paths_mean, dim3(nt, nt, (unsigned)H), dim3(256),
-                                        h->stream, bP.as<double>(), bB.as<double>(), bR.as<double>(), n, N,
-                                        (int)(s0 == 0), (int)(s0 + n == S), S, bSum.as<double>()));
+                                        h->stream, bP, bB, bR, n, N,
+                                        (int)(s0 == 0), (int)(s0 + n == S), S, bSum));
             HIPCHK(h, hipGetLastError());
         }
         if (paths)
-            HIPCHK(h, hipMemcpyAsync(hostP.data(), bP.p, (size_t)H * n * ND * sizeof(double), hipMemcpyDeviceToHost,
+            HIPCHK(h, hipMemcpyAsync(hostP.data(), bP, (size_t)H * n * ND * sizeof(double), hipMemcpyDeviceToHost,
                                      h->stream));
         if (labels)
-            HIPCHK(h, hipMemcpyAsync(hostL.data(), bLab.p, (size_t)H * n * N * sizeof(int32_t),
+            HIPCHK(h, hipMemcpyAsync(hostL.data(), bLab, (size_t)H * n * N * sizeof(int32_t),
                                      hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         for (int hh = 0; hh < H; ++hh)
@@ -128,7 +123,7 @@ int dlsm_forecast_paths(dlsm_chain *h, const double *X0, const double *intercept
                            (size_t)N * sizeof(int32_t));
             }
     }
-    HIPCHK(h, hipMemcpyAsync(probas, bSum.p, (size_t)H * N * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(probas, bSum, (size_t)H * N * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DLSM_OK;
 }

@@ -115,36 +115,35 @@ int dlsm_gof_dynamic_simulate(dlsm_chain *h, const double *Xs, const double *int
     int nb = batch > 0 ? batch : (int)std::max<size_t>(1, GOF_SCRATCH_BYTES / per_sample);
     nb = std::min(nb, S);
     nb = std::min(nb, std::max(1, 65535 / T));          // networks of a batch: the grid's y extent
-    DevBuf bX, bB, bR, bBits, bS;
-    HIPCHK(h, hipMalloc(&bX.p, (size_t)nb * T * N * D * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bB.p, (size_t)nb * 2 * sizeof(double)));
-    if (directed) HIPCHK(h, hipMalloc(&bR.p, (size_t)nb * N * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bBits.p, (size_t)nb * T * net_words * nmat * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&bS.p, (size_t)nb * sz.total() * sizeof(int64_t)));
+    DevArray<double> bX, bB, bR; DevArray<uint32_t> bBits;
+    DevArray<int64_t> bS;
+    if (bX.alloc(h, (size_t)nb * T * N * D) || bB.alloc(h, (size_t)nb * 2) ||
+        (directed && bR.alloc(h, (size_t)nb * N)) || bBits.alloc(h, (size_t)nb * T * net_words * nmat) ||
+        bS.alloc(h, (size_t)nb * sz.total())) return DLSM_E_HIP;
     const unsigned gx = (unsigned)((net_words + 255) / 256);
     for (int s0 = 0; s0 < S; s0 += nb) {
         const int n = std::min(nb, S - s0), nets = n * T;
-        HIPCHK(h, hipMemcpyAsync(bX.p, Xs + (size_t)s0 * T * N * D, (size_t)nets * N * D * sizeof(double),
+        HIPCHK(h, hipMemcpyAsync(bX, Xs + (size_t)s0 * T * N * D, (size_t)nets * N * D * sizeof(double),
                                  hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(bB.p, intercepts + 2 * (size_t)s0, (size_t)n * 2 * sizeof(double),
+        HIPCHK(h, hipMemcpyAsync(bB, intercepts + 2 * (size_t)s0, (size_t)n * 2 * sizeof(double),
                                  hipMemcpyHostToDevice, h->stream));
         if (directed)
-            HIPCHK(h, hipMemcpyAsync(bR.p, radii + (size_t)s0 * N, (size_t)n * N * sizeof(double),
+            HIPCHK(h, hipMemcpyAsync(bR, radii + (size_t)s0 * N, (size_t)n * N * sizeof(double),
                                      hipMemcpyHostToDevice, h->stream));
         DISPATCH_D(h, D, hipLaunchKernelGGL((k_gof_draw<DD>), dim3(gx, nets, (unsigned)nmat), dim3(256), 0,
-                                            h->stream, bX.as<double>(), bB.as<double>(),
-                                            directed ? bR.as<double>() : nullptr, T, N, W, (int)directed,
-                                            seed, first_index + (uint32_t)s0, bBits.as<uint32_t>()));
+                                            h->stream, bX, bB,
+                                            directed ? bR.get() : nullptr, T, N, W, (int)directed,
+                                            seed, first_index + (uint32_t)s0, bBits));
         HIPCHK(h, hipGetLastError());
-        const uint32_t *rows = bBits.as<uint32_t>();
+        const uint32_t *rows = bBits;
         rc = gof_dynamic_launch(h, rows, directed ? rows + (size_t)nets * net_words : nullptr, n, temporal, geo,
-                                bS.as<int64_t>());
+                                bS);
         if (rc) return rc;
         if (bits)
             HIPCHK(h, hipMemcpyAsync(bits + (size_t)s0 * T * net_words, rows,
                                      (size_t)nets * net_words * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                      h->stream));
-        rc = gof_dynamic_fetch(h, bS.as<int64_t>(), n, (size_t)s0, temporal, geo, overlap, steps, geodesic);
+        rc = gof_dynamic_fetch(h, bS, n, (size_t)s0, temporal, geo, overlap, steps, geodesic);
         if (rc) return rc;
     }
     return DLSM_OK;
@@ -165,21 +164,20 @@ int dlsm_gof_dynamic_observed(dlsm_chain *h, const uint32_t *bits, int64_t *over
     const bool directed = h->model != DLSM_UNDIRECTED;
     const bool need_t = directed && temporal && T > 1;          // only the shared partners read the columns
     const GofDynSizes sz(T, N, temporal, geo);
-    DevBuf bBits, bT, bS;
-    HIPCHK(h, hipMalloc(&bBits.p, (size_t)T * net_words * sizeof(uint32_t)));
-    if (need_t) HIPCHK(h, hipMalloc(&bT.p, (size_t)T * net_words * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&bS.p, sz.total() * sizeof(int64_t)));
-    HIPCHK(h, hipMemcpyAsync(bBits.p, bits, (size_t)T * net_words * sizeof(uint32_t), hipMemcpyHostToDevice,
+    DevArray<uint32_t> bBits, bT; DevArray<int64_t> bS;
+    if (bBits.alloc(h, (size_t)T * net_words) || (need_t && bT.alloc(h, (size_t)T * net_words)) ||
+        bS.alloc(h, sz.total())) return DLSM_E_HIP;
+    HIPCHK(h, hipMemcpyAsync(bBits, bits, (size_t)T * net_words * sizeof(uint32_t), hipMemcpyHostToDevice,
                              h->stream));
     if (need_t) {
         hipLaunchKernelGGL(k_gof_transpose, dim3((unsigned)((net_words + 255) / 256), T), dim3(256), 0,
-                           h->stream, bBits.as<uint32_t>(), N, W, bT.as<uint32_t>());
+                           h->stream, bBits, N, W, bT);
         HIPCHK(h, hipGetLastError());
     }
-    rc = gof_dynamic_launch(h, bBits.as<uint32_t>(), need_t ? bT.as<uint32_t>() : nullptr, 1, temporal, geo,
-                            bS.as<int64_t>());
+    rc = gof_dynamic_launch(h, bBits, need_t ? bT.get() : nullptr, 1, temporal, geo,
+                            bS);
     if (rc) return rc;
-    return gof_dynamic_fetch(h, bS.as<int64_t>(), 1, 0, temporal, geo, overlap, steps, geodesic);
+    return gof_dynamic_fetch(h, bS, 1, 0, temporal, geo, overlap, steps, geodesic);
 }
 
 }  // extern "C"

@@ -4,38 +4,14 @@
 
 namespace {
 
-// carve the loop's auxiliary buffers out of one allocation
+// the loop's auxiliary buffers, carved out of one allocation (workspace.hpp)
 HdpLoopBuf hdp_loop_buf(dlsm_chain *h) {
-    const size_t T = h->T, K = h->K, D = h->D;
     HdpLoopBuf b;
-    double *p = h->hdp_buf;
-    b.beta = p; p += K;
-    b.mbar = p; p += K;
-    b.S = p; p += T * K * D;
-    b.Q = p; p += T * K;
-    b.L = p; p += 2 * T * K;
-    b.LP = p; p += T * K;
-    b.LPD = p; p += T * K;
-    b.scr = p; p += HS_COUNT;
-    b.m = (int32_t *)p;
-    b.wover = b.m + T * K * K;
+    Carve at(h->hdp_buf); hdp_loop_layout(at, b, h->T, h->K, h->D, HS_COUNT);
     b.w = h->lab_w; b.n = h->lab_n; b.nk = h->lab_nk;
     b.mu = h->mu; b.sigma = h->sigma;
-    b.K = (int)K;
+    b.K = h->K;
     return b;
-}
-
-size_t hdp_loop_buf_doubles(const dlsm_chain *h) {
-    const size_t T = h->T, K = h->K, D = h->D;
-    return 2 * K + T * K * D + 5 * T * K + HS_COUNT + (T * K * K + T * K + 1) / 2 + 2;
-}
-
-void hdp_free_trace(dlsm_chain *h) {
-    void *ptrs[] = {h->htr_mu, h->htr_sigma, h->htr_beta, h->htr_w, h->htr_lambda, h->htr_hyper,
-                    h->htr_z};
-    for (void *p : ptrs) if (p) hipFree(p);
-    h->htr_mu = h->htr_sigma = h->htr_beta = h->htr_w = h->htr_lambda = h->htr_hyper = nullptr;
-    h->htr_z = nullptr; h->htr_n = 0; h->htr_K = 0;
 }
 
 // "queue `s` goes on when flags[which] has reached the ticket": a wait of the QUEUE itself
@@ -84,7 +60,7 @@ int enqueue_hdp_iteration(dlsm_chain *h, const Call &c, int it, bool draw_next) 
     HdpLoopBuf hb = hdp_loop_buf(h);
     HdpFork fk{nullptr, 0, 0, nullptr};
     // (budget: polls of ~1 us of the waits INSIDE kernels - kernels_hdploop.hpp, HdpFork; DLSM_HDP_FORK_BUDGET)
-    if (fork) fk = HdpFork{h->fork_flags, ++h->fork_ticket, c.knobs.hdp_fork_budget, h->fork_err_dev};
+    if (fork) fk = HdpFork{h->fork_flags, ++h->fork_ticket, c.knobs.hdp_fork_budget, h->fork_err.dev()};
     {   // label block update (sample_labels.py:134-190) with the transition matrices on the device
         ProfScope ps(h, DLSM_K_LABELS);
         rc = launch_sample_labels<DD>(h, v, (uint32_t)it, nullptr, h->stream,
@@ -199,9 +175,9 @@ int hdp_fork_arm(dlsm_chain *h, const Knobs &kn) {
         // workgroups per CU with unused LDS changes nothing; a CU mask of 160 is +0.5 %, 192 .. 240 are -1 %)
         HIPCHK(h, hipStreamCreateWithPriority(&h->fork_stream, hipStreamNonBlocking, lo));
         HIPCHK(h, hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
-        HIPCHK(h, hipMalloc((void **)&h->fork_flags, 64));
+        { int rc = h->fork_flags.alloc(h, 16); if (rc) return rc; }
         HIPCHK(h, hipMemset(h->fork_flags, 0, 64));
-        NEED(h, h->fork_err_dev != nullptr, "no mapped host memory for the error word of the in-kernel waits");
+        NEED(h, h->fork_err.dev() != nullptr, "no mapped host memory for the error word of the in-kernel waits");
         int can = 0;
         if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, h->device) != hipSuccess) can = 0;
         (void)hipGetLastError();
@@ -239,14 +215,10 @@ int dlsm_hdp_configure(dlsm_chain *h, const dlsm_hdp_config *cfg, const double *
     rc = check_sweep_algo(h, cfg->sweep_algo); if (rc) return rc;
     const int T = h->T, K = h->K;
     rc = ensure_label_bufs(h); if (rc) return rc;
-    const size_t need = hdp_loop_buf_doubles(h);
-    if (h->hdp_buf_cap < need) {
-        if (h->hdp_buf) hipFree(h->hdp_buf);
-        h->hdp_buf = nullptr; h->hdp_buf_cap = 0;
-        rc = dev_alloc(h, &h->hdp_buf, need); if (rc) return rc;
-        h->hdp_buf_cap = need;
-    }
-    HIPCHK(h, hipMemsetAsync(h->hdp_buf, 0, need * sizeof(double), h->stream));
+    HdpLoopBuf sized;
+    Carve size; hdp_loop_layout(size, sized, T, K, h->D, HS_COUNT);
+    rc = ensure_workspace(h, h->hdp_buf, size); if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(h->hdp_buf, 0, size.bytes(), h->stream));
     h->hdp_K = K;
     // device state: everything but lmbda (dlsm_set_prior_mixture owns it)
     HdpDeviceState s;
@@ -332,15 +304,11 @@ int dlsm_hdp_trace_alloc(dlsm_chain *h, int n_total, double logp0) {
     NEED(h, h->hdp_K == h->K, "n_components changed since dlsm_hdp_configure: configure again");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = dlsm_trace_alloc(h, n_total, logp0); if (rc) return rc;   // Xs_, intercepts_, logps_
-    hdp_free_trace(h);
     const size_t T = h->T, N = h->N, K = h->K, D = h->D, n = n_total;
-    rc = dev_alloc(h, &h->htr_mu, n * K * D); if (rc) return rc;
-    rc = dev_alloc(h, &h->htr_sigma, n * K); if (rc) return rc;
-    rc = dev_alloc(h, &h->htr_beta, n * K); if (rc) return rc;
-    rc = dev_alloc(h, &h->htr_w, n * T * K * K); if (rc) return rc;
-    rc = dev_alloc(h, &h->htr_lambda, n); if (rc) return rc;
-    rc = dev_alloc(h, &h->htr_hyper, n * 6); if (rc) return rc;
-    rc = dev_alloc(h, &h->htr_z, n * T * N); if (rc) return rc;
+    h->htr_z.reset(); h->htr_n = 0; h->htr_K = 0;       // (no trace until all of it is there)
+    if (h->htr_mu.alloc(h, n * K * D) || h->htr_sigma.alloc(h, n * K) || h->htr_beta.alloc(h, n * K) ||
+        h->htr_w.alloc(h, n * T * K * K) || h->htr_lambda.alloc(h, n) || h->htr_hyper.alloc(h, n * 6) ||
+        h->htr_z.alloc(h, n * T * N)) return DLSM_E_HIP;
     h->htr_n = n_total; h->htr_K = (int)K;
     // row 0 = the current state
     HdpLoopBuf hb = hdp_loop_buf(h);

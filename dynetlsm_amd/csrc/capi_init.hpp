@@ -18,12 +18,11 @@ int run_smacof(dlsm_chain *h, int t, int n_init, const double *X0, int max_iter,
     const int N = h->N;
     const size_t per = (size_t)N * DD;
     const int nblk = (N + SM_ROWS - 1) / SM_ROWS;
-    DevBuf bX, bRec, bSt;
-    HIPCHK(h, hipMalloc(&bX.p, 2 * n_init * per * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bRec.p, (size_t)n_init * nblk * 2 * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bSt.p, n_init * sizeof(SmacofState)));
-    double *Xb[2] = {bX.as<double>(), bX.as<double>() + n_init * per};
-    HIPCHK(h, hipMemsetAsync(bSt.p, 0, n_init * sizeof(SmacofState), h->stream));
+    DevArray<double> bX, bRec; DevArray<SmacofState> bSt;
+    if (bX.alloc(h, 2 * n_init * per) || bRec.alloc(h, (size_t)n_init * nblk * 2) ||
+        bSt.alloc(h, n_init)) return DLSM_E_HIP;
+    double *Xb[2] = {bX, bX + n_init * per};
+    HIPCHK(h, hipMemsetAsync(bSt, 0, n_init * sizeof(SmacofState), h->stream));
     HIPCHK(h, hipMemcpyAsync(Xb[0], X0, n_init * per * sizeof(double), hipMemcpyHostToDevice,
                              h->stream));
     const uint16_t *hops = h->hops + (size_t)t * N * N;
@@ -33,12 +32,11 @@ int run_smacof(dlsm_chain *h, int t, int n_init, const double *X0, int max_iter,
         for (int p = 0; p <= max_iter; ++p) {
             hipLaunchKernelGGL((k_smacof_pass<DD>), dim3(nblk, n_init), dim3(SM_THREADS), 0,
                                h->stream, hops, N, Xb[p & 1], Xb[(p + 1) & 1],
-                               bRec.as<double>(), bSt.as<SmacofState>());
+                               bRec, bSt);
             hipLaunchKernelGGL(k_smacof_check, dim3(n_init), dim3(256), 0, h->stream,
-                               bRec.as<double>(), nblk, p, max_iter, eps,
-                               bSt.as<SmacofState>());
+                               bRec, nblk, p, max_iter, eps, bSt);
             if ((p & 15) == 15 && p < max_iter) {
-                HIPCHK(h, hipMemcpyAsync(st.data(), bSt.p, n_init * sizeof(SmacofState),
+                HIPCHK(h, hipMemcpyAsync(st.data(), bSt, n_init * sizeof(SmacofState),
                                          hipMemcpyDeviceToHost, h->stream));
                 HIPCHK(h, hipStreamSynchronize(h->stream));
                 bool all = true;
@@ -48,7 +46,7 @@ int run_smacof(dlsm_chain *h, int t, int n_init, const double *X0, int max_iter,
         }
     }
     HIPCHK(h, hipGetLastError());
-    int rc = d2h(h, st.data(), bSt.as<SmacofState>(), (size_t)n_init);
+    int rc = d2h(h, st.data(), bSt, (size_t)n_init);
     if (rc) return rc;
     for (int r = 0; r < n_init; ++r) {
         rc = d2h(h, X_out + r * per, Xb[st[r].answer] + r * per, per);
@@ -68,16 +66,12 @@ int run_gmds_step(dlsm_chain *h, int t, const double *X_prev, double lmbda, int 
     NEED(h, kmax >= DD, "max_lanczos must be at least n_features");
     NEED(h, (size_t)(kmax + 1) * sizeof(double) <= 60000, "max_lanczos too large");
     const double alpha_w = 1.0 / (1.0 + lmbda), beta_w = lmbda / (1.0 + lmbda);
-    DevBuf bQ, bV, bXp, bXo, bS;
-    HIPCHK(h, hipMalloc(&bQ.p, (size_t)(kmax + 1) * N * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bV.p, ((size_t)2 * N + 2 * kmax + 16) * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bXp.p, (size_t)N * DD * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bXo.p, (size_t)N * DD * sizeof(double)));
-    HIPCHK(h, hipMalloc(&bS.p, ((size_t)DD * kmax + DD) * sizeof(double)));
-    double *Q = bQ.as<double>();
-    double *wB = bV.as<double>(), *w = wB + N, *ab = w + N, *small = ab + 2 * kmax;
-    double *Xp = bXp.as<double>(), *Xo = bXo.as<double>();
-    double *S = bS.as<double>(), *theta_d = S + (size_t)DD * kmax;
+    DevArray<double> Q, bV, Xp, Xo, S;
+    if (Q.alloc(h, (size_t)(kmax + 1) * N) || bV.alloc(h, (size_t)2 * N + 2 * kmax + 16) ||
+        Xp.alloc(h, (size_t)N * DD) || Xo.alloc(h, (size_t)N * DD) ||
+        S.alloc(h, (size_t)DD * kmax + DD)) return DLSM_E_HIP;
+    double *wB = bV, *w = wB + N, *ab = w + N, *small = ab + 2 * kmax;
+    double *theta_d = S + (size_t)DD * kmax;
     HIPCHK(h, hipMemcpyAsync(Xp, X_prev, (size_t)N * DD * sizeof(double), hipMemcpyHostToDevice,
                              h->stream));
     const uint16_t *hops = h->hops + (size_t)t * N * N;
@@ -145,8 +139,7 @@ int dlsm_init_shortest_paths(dlsm_chain *h) {
     HIPCHK(h, hipSetDevice(h->device));
     const size_t n = (size_t)h->T * h->N * h->N;
     if (!h->hops) {
-        HIPCHK(h, hipMalloc((void **)&h->hops, n * sizeof(uint16_t)));
-        HIPCHK(h, hipMalloc((void **)&h->hops_max, h->T * sizeof(int)));
+        if (h->hops.alloc(h, n) || h->hops_max.alloc(h, h->T)) return DLSM_E_HIP;
     }
     HIPCHK(h, hipMemsetAsync(h->hops_max, 0, h->T * sizeof(int), h->stream));
     const size_t lds = (size_t)3 * h->W * sizeof(uint32_t) + (size_t)h->N * sizeof(uint16_t);
@@ -175,13 +168,13 @@ int dlsm_init_get_dissimilarity(dlsm_chain *h, int t, double *out) {
     NEED(h, t >= 0 && t < h->T, "t out of range");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t n2 = (size_t)h->N * h->N;
-    DevBuf b;
-    HIPCHK(h, hipMalloc(&b.p, n2 * sizeof(double)));
+    DevArray<double> b;
+    rc = b.alloc(h, n2); if (rc) return rc;
     const int nb = (int)std::min<size_t>(4096, (n2 + 255) / 256);
     hipLaunchKernelGGL(k_hops_to_double, dim3(nb), dim3(256), 0, h->stream,
-                       h->hops + (size_t)t * n2, n2, b.as<double>());
+                       h->hops + (size_t)t * n2, n2, b);
     HIPCHK(h, hipGetLastError());
-    return d2h(h, out, b.as<double>(), n2);
+    return d2h(h, out, b, n2);
 }
 
 int dlsm_init_smacof(dlsm_chain *h, int t, int n_init, const double *X0, int max_iter,
@@ -240,9 +233,7 @@ int dlsm_init_release(dlsm_chain *h) {
     NEED(h, h != nullptr, "null handle");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->hops) hipFree(h->hops);
-    if (h->hops_max) hipFree(h->hops_max);
-    h->hops = nullptr; h->hops_max = nullptr; h->have_hops = false;
+    h->hops.reset(); h->hops_max.reset(); h->have_hops = false;
     return DLSM_OK;
 }
 
@@ -254,18 +245,16 @@ int dlsm_init_kmeans_lloyd(dlsm_chain *h, const double *X, int N, int F, int K,
     const size_t lds = ((size_t)K * F + K) * sizeof(double);
     NEED(h, lds <= 64 * 1024, "the centres (n_clusters x T d doubles) do not fit the assignment kernel's LDS");
     HIPCHK(h, hipSetDevice(h->device));
-    DevBuf dX, dC, dL, dS;
-    HIPCHK(h, hipMalloc(&dX.p, (size_t)N * F * sizeof(double)));
-    HIPCHK(h, hipMalloc(&dC.p, (size_t)2 * K * F * sizeof(double)));
-    HIPCHK(h, hipMalloc(&dL.p, (size_t)N * sizeof(int32_t)));
-    HIPCHK(h, hipMalloc(&dS.p, (size_t)K * (sizeof(double) + sizeof(int32_t)) + 16));
-    double *cen[2] = {dC.as<double>(), dC.as<double>() + (size_t)K * F};
-    double *d_shift = dS.as<double>();
-    int32_t *d_counts = (int32_t *)(d_shift + K), *d_changed = d_counts + K;
-    HIPCHK(h, hipMemcpyAsync(dX.p, X, (size_t)N * F * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    DevArray<double> dX, dC, d_shift;
+    DevArray<int32_t> dL, d_counts;             // (d_counts: a count per centre, then the changed-labels word)
+    if (dX.alloc(h, (size_t)N * F) || dC.alloc(h, (size_t)2 * K * F) || dL.alloc(h, N) || d_shift.alloc(h, K) ||
+        d_counts.alloc(h, (size_t)K + 1)) return DLSM_E_HIP;
+    double *cen[2] = {dC, dC + (size_t)K * F};
+    int32_t *d_changed = d_counts + K;
+    HIPCHK(h, hipMemcpyAsync(dX, X, (size_t)N * F * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(cen[0], centers_init, (size_t)K * F * sizeof(double), hipMemcpyHostToDevice,
                              h->stream));
-    HIPCHK(h, hipMemsetAsync(dL.p, 0xFF, (size_t)N * sizeof(int32_t), h->stream));      // labels = -1
+    HIPCHK(h, hipMemsetAsync(dL, 0xFF, (size_t)N * sizeof(int32_t), h->stream));      // labels = -1
     std::vector<double> shift(K);
     std::vector<int32_t> counts(K + 1);
     const int nb = (N + 255) / 256;
@@ -278,10 +267,10 @@ int dlsm_init_kmeans_lloyd(dlsm_chain *h, const double *X, int N, int F, int K,
     // one more E-step so that the labels match the returned centres
     for (it = 0; it < max_iter; ++it) {
         HIPCHK(h, hipMemsetAsync(d_changed, 0, sizeof(int32_t), h->stream));
-        hipLaunchKernelGGL(k_kmeans_assign, dim3(nb), dim3(256), lds, h->stream, dX.as<double>(), N, F, K,
-                           cen[cur], dL.as<int32_t>(), d_changed);
-        hipLaunchKernelGGL(k_kmeans_update, dim3(K), dim3(256), 0, h->stream, dX.as<double>(), N, F,
-                           dL.as<int32_t>(), cen[cur], cen[cur ^ 1], d_counts, d_shift);
+        hipLaunchKernelGGL(k_kmeans_assign, dim3(nb), dim3(256), lds, h->stream, dX, N, F, K,
+                           cen[cur], dL, d_changed);
+        hipLaunchKernelGGL(k_kmeans_update, dim3(K), dim3(256), 0, h->stream, dX, N, F,
+                           dL, cen[cur], cen[cur ^ 1], d_counts, d_shift);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(shift.data(), d_shift, K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(counts.data(), d_counts, (K + 1) * sizeof(int32_t), hipMemcpyDeviceToHost,
@@ -297,14 +286,14 @@ int dlsm_init_kmeans_lloyd(dlsm_chain *h, const double *X, int N, int F, int K,
     }
     if (!strict) {
         HIPCHK(h, hipMemsetAsync(d_changed, 0, sizeof(int32_t), h->stream));
-        hipLaunchKernelGGL(k_kmeans_assign, dim3(nb), dim3(256), lds, h->stream, dX.as<double>(), N, F, K,
-                           cen[cur], dL.as<int32_t>(), d_changed);
+        hipLaunchKernelGGL(k_kmeans_assign, dim3(nb), dim3(256), lds, h->stream, dX, N, F, K,
+                           cen[cur], dL, d_changed);
         HIPCHK(h, hipGetLastError());
     }
     *n_iter_out = std::min(it, max_iter);
     HIPCHK(h, hipMemcpyAsync(centers_out, cen[cur], (size_t)K * F * sizeof(double), hipMemcpyDeviceToHost,
                              h->stream));
-    HIPCHK(h, hipMemcpyAsync(labels_out, dL.p, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(labels_out, dL, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DLSM_OK;
 }

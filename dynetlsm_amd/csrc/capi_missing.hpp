@@ -6,10 +6,8 @@
 namespace {
 
 void miss_free(dlsm_chain *h) {
-    void *ptrs[] = {h->miss_jobs, h->miss_cols, h->miss_slot, h->miss_psum, h->miss_ones, h->miss_nacc};
-    for (void *p : ptrs) if (p) hipFree(p);
-    h->miss_jobs = nullptr; h->miss_cols = h->miss_slot = nullptr;
-    h->miss_psum = nullptr; h->miss_ones = nullptr; h->miss_nacc = nullptr;
+    h->miss_jobs.reset(); h->miss_cols.reset(); h->miss_slot.reset();
+    h->miss_psum.reset(); h->miss_ones.reset(); h->miss_nacc.reset();
     h->miss_n = 0; h->miss_njobs = 0;
 }
 
@@ -26,9 +24,9 @@ int miss_check_ready(dlsm_chain *h) {
 template <int DD>
 int enqueue_impute(dlsm_chain *h, hipStream_t q, IterRef ir, int accumulate, uint32_t after) {
     MissArgs a;
-    a.jobs = (const MissJob *)h->miss_jobs; a.cols = h->miss_cols; a.slot = h->miss_slot;
+    a.jobs = (const MissJob *)h->miss_jobs.get(); a.cols = h->miss_cols; a.slot = h->miss_slot;
     a.ybits = h->ybits; a.ytbits = h->ytbits;
-    a.ycm32 = h->model == DLSM_UNDIRECTED ? (uint32_t *)h->ycm : nullptr;
+    a.ycm32 = h->model == DLSM_UNDIRECTED ? (uint32_t *)h->ycm.get() : nullptr;
     a.psum = h->miss_psum; a.ones = h->miss_ones; a.nacc = h->miss_nacc;
     a.accumulate = accumulate; a.acc_after = after;
     hipLaunchKernelGGL((k_impute_missing<DD>), dim3((unsigned)h->miss_njobs), dim3(64), 0, q, h->view(), a, ir);
@@ -90,12 +88,9 @@ int dlsm_set_missing(dlsm_chain *h, const int32_t *tij, int64_t n) {
     }
     jobs[jobs.size() - 1] = (int32_t)es.size();
     miss_free(h);
-    int rc = dev_alloc(h, &h->miss_jobs, jobs.size()); if (rc) return rc;
-    rc = dev_alloc(h, &h->miss_cols, cols.size()); if (rc) return rc;
-    rc = dev_alloc(h, &h->miss_slot, slot.size()); if (rc) return rc;
-    rc = dev_alloc(h, &h->miss_psum, (size_t)n); if (rc) return rc;
-    rc = dev_alloc(h, &h->miss_ones, (size_t)n); if (rc) return rc;
-    rc = dev_alloc(h, &h->miss_nacc, 1); if (rc) return rc;
+    if (h->miss_jobs.alloc(h, jobs.size()) || h->miss_cols.alloc(h, cols.size()) ||
+        h->miss_slot.alloc(h, slot.size()) || h->miss_psum.alloc(h, (size_t)n) || h->miss_ones.alloc(h, (size_t)n) ||
+        h->miss_nacc.alloc(h, 1)) return DLSM_E_HIP;
     HIPCHK(h, hipMemcpy(h->miss_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->miss_cols, cols.data(), cols.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->miss_slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));

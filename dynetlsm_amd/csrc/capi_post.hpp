@@ -1,5 +1,4 @@
-// C-ABI of the post-loop processing (included by capi.hip, which provides DevBuf and
-// the FAIL / HIPCHK / NEED macros).
+// C-ABI of the post-loop processing (included by capi.hip, which provides the FAIL / HIPCHK / NEED macros).
 #pragma once
 
 extern "C" {
@@ -8,9 +7,7 @@ int dlsm_post_release(dlsm_chain *h) {
     NEED(h, h != nullptr, "null handle");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->post_zt) hipFree(h->post_zt);
-    if (h->post_cooc) hipFree(h->post_cooc);
-    h->post_zt = nullptr; h->post_cooc = nullptr; h->post_S = h->post_Spad = 0;
+    h->post_zt.reset(); h->post_cooc.reset(); h->post_S = h->post_Spad = 0;
     return DLSM_OK;
 }
 
@@ -26,32 +23,30 @@ int dlsm_post_cooccurrence(dlsm_chain *h, const int64_t *zs, int S, int K, doubl
     int rc = dlsm_post_release(h); if (rc) return rc;
     const int Spad = (S + 63) / 64 * 64;
     const size_t n2 = (size_t)T * N * N;
-    HIPCHK(h, hipMalloc((void **)&h->post_zt, per * Spad));
-    HIPCHK(h, hipMalloc((void **)&h->post_cooc, n2 * sizeof(double)));
+    if (h->post_zt.alloc(h, per * Spad) || h->post_cooc.alloc(h, n2)) return DLSM_E_HIP;
     HIPCHK(h, hipMemsetAsync(h->post_zt, 0, per * Spad, h->stream));
     h->post_S = S; h->post_Spad = Spad;
     // labels: staged in chunks of samples, packed to bytes and transposed on the device
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(S, ((size_t)64 << 20) / (per * 8)));
-    DevBuf stage, counts;
-    HIPCHK(h, hipMalloc(&stage.p, (size_t)chunk * per * sizeof(int64_t)));
-    HIPCHK(h, hipMalloc(&counts.p, n2 * sizeof(uint32_t)));
+    DevArray<int64_t> stage; DevArray<uint32_t> counts;
+    if (stage.alloc(h, (size_t)chunk * per) || counts.alloc(h, n2)) return DLSM_E_HIP;
     {
         ProfScope ps(h, DLSM_K_LABELS);
         for (int s0 = 0; s0 < S; s0 += chunk) {
             const int ns = std::min(chunk, S - s0);
-            HIPCHK(h, hipMemcpyAsync(stage.p, zs + (size_t)s0 * per, (size_t)ns * per * sizeof(int64_t),
+            HIPCHK(h, hipMemcpyAsync(stage, zs + (size_t)s0 * per, (size_t)ns * per * sizeof(int64_t),
                                      hipMemcpyHostToDevice, h->stream));
             const int nb = (int)std::min<size_t>(4096, ((size_t)ns * per + 255) / 256);
             hipLaunchKernelGGL(k_post_pack_labels<int64_t>, dim3(nb), dim3(256), 0, h->stream,
-                               stage.as<int64_t>(), ns, s0, T, N, Spad, h->post_zt);
+                               stage, ns, s0, T, N, Spad, h->post_zt);
             HIPCHK(h, hipStreamSynchronize(h->stream));     // the staging buffer is reused
         }
         const int nt = (N + PC_TILE - 1) / PC_TILE;
         hipLaunchKernelGGL(k_post_cooccurrence, dim3(nt, nt, T), dim3(256), 0, h->stream,
-                           h->post_zt, N, S, Spad, counts.as<uint32_t>());
+                           h->post_zt, N, S, Spad, counts);
         const int nb = (int)std::min<size_t>(8192, (n2 + 255) / 256);
         hipLaunchKernelGGL(k_post_counts_to_proba, dim3(nb), dim3(256), 0, h->stream,
-                           counts.as<uint32_t>(), n2, (double)S, h->post_cooc);
+                           counts, n2, (double)S, h->post_cooc);
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -65,18 +60,17 @@ int dlsm_post_expected_vi_sums(dlsm_chain *h, double *out) {
     HIPCHK(h, hipSetDevice(h->device));
     const int T = h->T, N = h->N, S = h->post_S, Spad = h->post_Spad;
     const int ngroups = (N + PV_ROWS_PER_WG - 1) / PV_ROWS_PER_WG;
-    DevBuf part, res;
-    HIPCHK(h, hipMalloc(&part.p, (size_t)T * ngroups * Spad * sizeof(double)));
-    HIPCHK(h, hipMalloc(&res.p, (size_t)T * S * sizeof(double)));
+    DevArray<double> part, res;
+    if (part.alloc(h, (size_t)T * ngroups * Spad) || res.alloc(h, (size_t)T * S)) return DLSM_E_HIP;
     {
         ProfScope ps(h, DLSM_K_LABELS);
         hipLaunchKernelGGL(k_post_vi_rows, dim3(ngroups, Spad / 64, T), dim3(256), 0, h->stream,
-                           h->post_zt, h->post_cooc, N, S, Spad, part.as<double>());
+                           h->post_zt, h->post_cooc, N, S, Spad, part);
         hipLaunchKernelGGL(k_post_vi_reduce, dim3((S + 255) / 256, T), dim3(256), 0, h->stream,
-                           part.as<double>(), ngroups, S, Spad, res.as<double>());
+                           part, ngroups, S, Spad, res);
     }
     HIPCHK(h, hipGetLastError());
-    return d2h(h, out, res.as<double>(), (size_t)T * S);
+    return d2h(h, out, res, (size_t)T * S);
 }
 
 // ---- the same processing on the device-resident trace of dlsm_hdp_run ---------------------------
@@ -94,20 +88,20 @@ int dlsm_post_trace_label_counts(dlsm_chain *h, int first, int count, int32_t *n
     NEED(h, h->htr_K <= 256, "n_components beyond 256");
     HIPCHK(h, hipSetDevice(h->device));
     const int T = h->T, N = h->N, K = h->htr_K;
-    DevBuf out;
+    DevArray<int32_t> out;
     const size_t n = (size_t)count * T * K;
-    HIPCHK(h, hipMalloc(&out.p, n * sizeof(int32_t)));
+    rc = out.alloc(h, n); if (rc) return rc;
     {
         ProfScope ps(h, DLSM_K_LABELS);
         // (the rows go on the x extent, capped: the kernel strides over what is left)
         const size_t rows = (size_t)count * T;
         const unsigned nb = (unsigned)std::min<size_t>(rows, (size_t)1 << 20);
         hipLaunchKernelGGL(k_post_label_counts, dim3(nb), dim3(256), 0, h->stream,
-                           h->htr_z + (size_t)first * T * N, rows, N, K, out.as<int32_t>());
+                           h->htr_z + (size_t)first * T * N, rows, N, K, out);
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(nk, out.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(nk, out, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return DLSM_OK;
 }
 
@@ -120,13 +114,11 @@ int dlsm_post_trace_cooccurrence(dlsm_chain *h, int first, int count, double *co
     rc = dlsm_post_release(h); if (rc) return rc;
     const int Spad = (S + 63) / 64 * 64;
     const size_t n2 = (size_t)T * N * N;
-    HIPCHK(h, hipMalloc((void **)&h->post_zt, per * Spad));
-    HIPCHK(h, hipMalloc((void **)&h->post_cooc, n2 * sizeof(double)));
+    if (h->post_zt.alloc(h, per * Spad) || h->post_cooc.alloc(h, n2)) return DLSM_E_HIP;
     HIPCHK(h, hipMemsetAsync(h->post_zt, 0, per * Spad, h->stream));
     h->post_S = S; h->post_Spad = Spad;
-    DevBuf counts, sums;
-    HIPCHK(h, hipMalloc(&counts.p, n2 * sizeof(uint32_t)));
-    HIPCHK(h, hipMalloc(&sums.p, per * sizeof(double)));
+    DevArray<uint32_t> counts; DevArray<double> sums;
+    if (counts.alloc(h, n2) || sums.alloc(h, per)) return DLSM_E_HIP;
     {
         ProfScope ps(h, DLSM_K_LABELS);
         const int nbp = (int)std::min<size_t>(8192, ((size_t)S * per + 255) / 256);
@@ -134,16 +126,16 @@ int dlsm_post_trace_cooccurrence(dlsm_chain *h, int first, int count, double *co
                            h->htr_z + (size_t)first * per, S, 0, T, N, Spad, h->post_zt);
         const int nt = (N + PC_TILE - 1) / PC_TILE;
         hipLaunchKernelGGL(k_post_cooccurrence, dim3(nt, nt, T), dim3(256), 0, h->stream,
-                           h->post_zt, N, S, Spad, counts.as<uint32_t>());
+                           h->post_zt, N, S, Spad, counts);
         const int nb = (int)std::min<size_t>(8192, (n2 + 255) / 256);
         hipLaunchKernelGGL(k_post_counts_to_proba, dim3(nb), dim3(256), 0, h->stream,
-                           counts.as<uint32_t>(), n2, (double)S, h->post_cooc);
+                           counts, n2, (double)S, h->post_cooc);
         hipLaunchKernelGGL(k_post_row_sums, dim3((unsigned)((per + 3) / 4)), dim3(256), 0, h->stream,
-                           h->post_cooc, per, N, sums.as<double>());
+                           h->post_cooc, per, N, sums);
     }
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (row_sums) { rc = d2h(h, row_sums, sums.as<double>(), per); if (rc) return rc; }
+    if (row_sums) { rc = d2h(h, row_sums, sums, per); if (rc) return rc; }
     if (cooc_out) return d2h(h, cooc_out, h->post_cooc, n2);
     return DLSM_OK;
 }
@@ -161,7 +153,7 @@ int dlsm_post_trace_align(dlsm_chain *h, int first, int count, int ref_row) {
     HIPCHK(h, hipSetDevice(h->device));
     const int T = h->T, N = h->N, D = h->D, K = h->htr_K;
     const size_t row = (size_t)T * N * D;
-    if (!h->xref) { rc = dev_alloc(h, &h->xref, row); if (rc) return rc; }
+    if (!h->xref) { rc = h->xref.alloc(h, row); if (rc) return rc; }
     // the reference is one of the rows: aligned onto a copy of itself (its rotation is the identity)
     HIPCHK(h, hipMemcpyAsync(h->xref, h->trace_X + row * ref_row, row * sizeof(double),
                              hipMemcpyDeviceToDevice, h->stream));
@@ -181,16 +173,15 @@ int dlsm_post_trace_mean(dlsm_chain *h, int first, int count, double *X_mean) {
     NEED(h, X_mean != nullptr, "null argument");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t row = (size_t)h->T * h->N * h->D;
-    DevBuf part, out;
-    HIPCHK(h, hipMalloc(&part.p, (size_t)PM_CHUNKS * row * sizeof(double)));
-    HIPCHK(h, hipMalloc(&out.p, row * sizeof(double)));
+    DevArray<double> part, out;
+    if (part.alloc(h, (size_t)PM_CHUNKS * row) || out.alloc(h, row)) return DLSM_E_HIP;
     const unsigned nb = (unsigned)((row + 255) / 256);
     hipLaunchKernelGGL(k_post_mean_partial, dim3(nb, PM_CHUNKS), dim3(256), 0, h->stream,
-                       h->trace_X + row * first, row, count, part.as<double>());
-    hipLaunchKernelGGL(k_post_mean_final, dim3(nb), dim3(256), 0, h->stream, part.as<double>(), row,
-                       count, out.as<double>());
+                       h->trace_X + row * first, row, count, part);
+    hipLaunchKernelGGL(k_post_mean_final, dim3(nb), dim3(256), 0, h->stream, part, row,
+                       count, out);
     HIPCHK(h, hipGetLastError());
-    return d2h(h, X_mean, out.as<double>(), row);
+    return d2h(h, X_mean, out, row);
 }
 
 int dlsm_post_latent_marginal_loglik(dlsm_chain *h, int row, const double *init_w,
@@ -204,21 +195,20 @@ int dlsm_post_latent_marginal_loglik(dlsm_chain *h, int row, const double *init_
     const int T = h->T, N = h->N, D = h->D;
     const size_t n_w = (size_t)T * K * K, n_mu = (size_t)K * D;
     const int nwg = (N + 3) / 4;
-    DevBuf par, part;
-    HIPCHK(h, hipMalloc(&par.p, (K + n_w + n_mu + K) * sizeof(double)));
-    HIPCHK(h, hipMalloc(&part.p, (size_t)nwg * sizeof(double)));
-    double *d_init = par.as<double>(), *d_w = d_init + K, *d_mu = d_w + n_w, *d_sig = d_mu + n_mu;
+    DevArray<double> par, part;
+    if (par.alloc(h, K + n_w + n_mu + K) || part.alloc(h, nwg)) return DLSM_E_HIP;
+    double *d_init = par, *d_w = d_init + K, *d_mu = d_w + n_w, *d_sig = d_mu + n_mu;
     HIPCHK(h, hipMemcpyAsync(d_init, init_w, K * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_w, trans_w, n_w * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_mu, mu, n_mu * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_sig, sigma, K * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const double *X = row >= 0 ? h->trace_X + (size_t)T * N * D * row : h->X;
     DISPATCH_D(h, D, hipLaunchKernelGGL((k_post_forward_loglik<DD>), dim3(nwg), dim3(256), 0, h->stream,
-                                        X, T, N, d_init, d_w, d_mu, d_sig, lmbda, K, part.as<double>()));
+                                        X, T, N, d_init, d_w, d_mu, d_sig, lmbda, K, part));
     HIPCHK(h, hipGetLastError());
     std::vector<double> hp(nwg);
     HIPCHK(h, hipStreamSynchronize(h->stream));     // the caller's parameter arrays are free again
-    HIPCHK(h, hipMemcpy(hp.data(), part.p, nwg * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(hp.data(), part, nwg * sizeof(double), hipMemcpyDeviceToHost));
     double tot = 0.0;
     for (int g = 0; g < nwg; ++g) tot += hp[g];     // fixed order
     *out = tot;

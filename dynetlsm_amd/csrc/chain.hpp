@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/dynetlsm_hip.h"
+#include "device_mem.hpp"
 
 namespace dlsm {
 
@@ -113,79 +114,78 @@ struct ProfileSlot {
 }  // namespace dlsm
 
 struct dlsm_chain {
+    template <typename T> using Dev = dlsm::DevArray<T>;
     int device = 0;
     int T = 0, N = 0, D = 0, model = 0, squared = 0;
     uint64_t seed = 0; uint32_t chain = 0;
     hipStream_t stream = nullptr;
-    void *stage = nullptr;                  // pinned host staging for the small copies of the C-ABI
+    dlsm::HostArray<char> stage;            // pinned host staging for the small copies of the C-ABI
     // HDP-LPCM loop, undirected: the intercept's likelihood pass on a queue of its own beside the label
     // update and the conjugate draws, handed over through device flags (kernels_hdploop.hpp, HdpFork)
     hipStream_t fork_stream = nullptr; hipEvent_t fork_ev = nullptr;
-    int32_t *fork_flags = nullptr; int32_t fork_ticket = 0; bool fork_armed = false;
-    int32_t *fork_err_host = nullptr, *fork_err_dev = nullptr;      // sticky error word (mapped host memory)
+    Dev<int32_t> fork_flags; int32_t fork_ticket = 0; bool fork_armed = false;
+    dlsm::HostArray<int32_t> fork_err;      // sticky error word (mapped host memory: get() here, dev() in kernels)
     bool fork_wait_value = false;           // the queues' waits are hipStreamWaitValue32 (else the gate kernel)
     // network
     int W = 0;
-    uint32_t *ybits = nullptr, *ytbits = nullptr;
-    unsigned long long *ycm = nullptr;      // undirected: column-block-major copy of ybits
+    Dev<uint32_t> ybits, ytbits;
+    Dev<unsigned long long> ycm;            // undirected: column-block-major copy of ybits
     bool have_network = false;
     int Din = 0, Dout = 0, C = 0;
-    int32_t *in_edges = nullptr, *out_edges = nullptr, *degree = nullptr;
-    int32_t *ctrl_in = nullptr, *ctrl_out = nullptr;
+    Dev<int32_t> in_edges, out_edges, degree;
+    Dev<int32_t> ctrl_in, ctrl_out;
     bool have_edges = false, have_controls = false;
     // state
-    double *X = nullptr, *intercept = nullptr, *radii = nullptr, *radii_alt = nullptr;
+    Dev<double> X, intercept, radii, radii_alt;
     bool have_X = false, have_radii = false;
-    double *step = nullptr; int32_t *nacc = nullptr, *nsteps = nullptr, *until = nullptr;
+    Dev<double> step; Dev<int32_t> nacc, nsteps, until;
     int tune = -1, tune_interval = 100;
     bool have_samplers = false;
     int prior_kind = 0; double tau_sq = 2.0, sigma_sq = 0.1;
-    double *mu = nullptr, *sigma = nullptr; double lmbda = 0.0; int32_t *z = nullptr;
-    dlsm::HdpDeviceState *hdp = nullptr;    // device; always allocated (holds lmbda)
-    // device-resident HDP-LPCM loop: auxiliary buffers and traces
-    double *hdp_buf = nullptr; size_t hdp_buf_cap = 0; int hdp_K = 0;
+    Dev<double> mu, sigma; double lmbda = 0.0; Dev<int32_t> z;
+    Dev<dlsm::HdpDeviceState> hdp;          // always allocated (holds lmbda)
+    // device-resident HDP-LPCM loop: auxiliary buffers (workspace.hpp, hdp_loop_layout) and traces
+    Dev<double> hdp_buf; int hdp_K = 0;
     bool hdp_configured = false;
     dlsm_hdp_config hdp_cfg{};
-    double *htr_mu = nullptr, *htr_sigma = nullptr, *htr_beta = nullptr, *htr_w = nullptr,
-           *htr_lambda = nullptr, *htr_hyper = nullptr;
-    uint8_t *htr_z = nullptr;
+    Dev<double> htr_mu, htr_sigma, htr_beta, htr_w, htr_lambda, htr_hyper;
+    Dev<uint8_t> htr_z;
     int htr_n = 0, htr_K = 0;
     int K = 0; bool have_prior = false;
     // scratch
-    double *partials = nullptr; size_t partials_cap = 0;   // doubles
-    double *xr = nullptr; size_t xr_cap = 0;               // packed (x, r, r') records (case-control)
-    double *dsmall = nullptr;      // 128 doubles of device scratch ([64, 128): a d x d rotation, d <= 8)
-    double *hsmall = nullptr;      // 64 doubles of pinned host scratch
-    double *xref = nullptr;        // T*N*D (procrustes reference staging)
-    int32_t *lab_n = nullptr, *lab_nk = nullptr; double *lab_w = nullptr;
-    size_t lab_cap = 0;                                    // T*K*K the three were sized for
-    // sweep v2 scratch
-    double *spec = nullptr; size_t spec_cap = 0;
-    double *pipe = nullptr; size_t pipe_cap = 0;        // pipelined sweep (algo 4) buffers
+    Dev<double> partials;
+    Dev<double> xr;                // packed (x, r, r') records (case-control)
+    Dev<double> dsmall;            // 128 doubles of device scratch ([64, 128): a d x d rotation, d <= 8)
+    dlsm::HostArray<double> hsmall;         // 64 doubles of pinned host scratch
+    Dev<double> xref;              // T*N*D (procrustes reference staging)
+    Dev<int32_t> lab_n, lab_nk; Dev<double> lab_w;         // lab_n, lab_w: the T*K*K they were sized for
+    // sweep v2 scratch (workspace.hpp: spec_layout; pipe_layout / ccpipe_layout)
+    Dev<double> spec;
+    Dev<double> pipe;                                   // pipelined sweeps (algo 4, algo 5) buffers
     int pipe_head_q = 0;                                // nodes per evaluator workgroup of its last head launch (0: none yet)
     dlsm::SweepCarry carry;
     int n_cu = 256;
-    int32_t *nctrl = nullptr; size_t nctrl_cap = 0;     // valid controls per (t, i, dir)
+    Dev<int32_t> nctrl;                                 // valid controls per (t, i, dir)
     bool nctrl_valid = false;
     // case-control model: a node's counts, control weights and its four index lists as one row (cc_rows.hpp)
-    int32_t *cc_terms = nullptr; size_t cc_terms_cap = 0; bool cc_terms_valid = false; int cc_tw = 0;
+    Dev<int32_t> cc_terms; bool cc_terms_valid = false; int cc_tw = 0;
     // the likelihood pass's walking order (cc_rows.hpp, k_cc_order): entries, then a count per slice
-    int32_t *cc_order = nullptr, *cc_order_cnt = nullptr; size_t cc_order_cap = 0; int cc_emax = 0;
-    int32_t *cc_pos = nullptr; size_t cc_pos_cap = 0;        // where a node's row lies (cc_rows.hpp: k_cc_pos)
-    unsigned long long *stamps = nullptr;               // in-kernel timestamps (profiling)
-    size_t stamps_cap = 0, stamps_used = 0;             // in [start, end] pairs
+    Dev<int32_t> cc_order; int32_t *cc_order_cnt = nullptr; int cc_emax = 0;
+    Dev<int32_t> cc_pos;                                     // where a node's row lies (cc_rows.hpp: k_cc_pos)
+    Dev<unsigned long long> stamps;                     // in-kernel timestamps (profiling): [start, end] pairs
+    size_t stamps_used = 0;                             // in pairs
     std::vector<std::pair<size_t, size_t>> stamp_launches;   // (first pair, pairs) per launch
     // initialisation pipeline: hop matrices [T][N][N] and the per-slice maximum
-    uint16_t *hops = nullptr; int *hops_max = nullptr; bool have_hops = false;
+    Dev<uint16_t> hops; Dev<int> hops_max; bool have_hops = false;
     // post-loop processing: labels of the kept samples (bytes, [T][N][Spad]) and the
     // co-occurrence probabilities [T][N][N]
-    uint8_t *post_zt = nullptr; double *post_cooc = nullptr; int post_S = 0, post_Spad = 0;
+    Dev<uint8_t> post_zt; Dev<double> post_cooc; int post_S = 0, post_Spad = 0;
     // LSM device-resident chain
-    dlsm::LsmDeviceState *lsm = nullptr;
+    Dev<dlsm::LsmDeviceState> lsm;
     dlsm_lsm_config lsm_cfg{};
     bool lsm_configured = false;
-    double *trace_X = nullptr, *trace_ic = nullptr, *trace_logp = nullptr;
-    double *trace_radii = nullptr;
+    Dev<double> trace_X, trace_ic, trace_logp;
+    Dev<double> trace_radii;
     int trace_n = 0;
     // one captured Gibbs iteration (hipGraph), replayed by dlsm_lsm_run
     hipGraph_t graph = nullptr; hipGraphExec_t graph_exec = nullptr;
@@ -193,8 +193,8 @@ struct dlsm_chain {
     // missing-dyad imputation (kernels_missing.hpp): per-(matrix, t, row) segments of the list in both
     // orientations, the accumulators per listed dyad, and whether dlsm_lsm_run ends its iterations with the step
     int64_t miss_n = 0; int miss_njobs = 0;
-    int32_t *miss_jobs = nullptr, *miss_cols = nullptr, *miss_slot = nullptr;
-    double *miss_psum = nullptr; uint32_t *miss_ones = nullptr; unsigned long long *miss_nacc = nullptr;
+    Dev<int32_t> miss_jobs, miss_cols, miss_slot;
+    Dev<double> miss_psum; Dev<uint32_t> miss_ones; Dev<unsigned long long> miss_nacc;
     bool miss_on = false; int64_t miss_after = 0;
     // measurement
     bool profiling = false;
