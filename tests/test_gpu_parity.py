@@ -742,15 +742,18 @@ def test_labels_medium_and_distribution(eng):
         np.testing.assert_allclose(lp, st.node_logp(1, 5, X[1, 5]), rtol=1e-12)
 
 
+# The kernel each case reaches today (the matrix-core kernel takes K <= 32 while its tables fit in 150 KB of LDS,
+# 8 nodes per workgroup; tests/labels_ref.py: form restates the dispatch, and tests/test_gpu_labels_shapes.py
+# holds every form to the long-double replica draw for draw at the shapes that cross its boundaries):
 @pytest.mark.parametrize('T,N,D,K', [
-    (10, 301, 2, 40),     # transition matrices too large for LDS: read from global memory
-    (70, 50, 1, 3),       # more than 64 time steps: the uniforms come in two passes
-    (3, 77, 3, 64),       # every lane owns a component; N not a multiple of the group size
-    (1, 9, 2, 2),         # a single time step: no backward pass
+    (10, 301, 2, 40),     # wavefront kernel, transition matrices too large for LDS: read from global memory
+    (70, 50, 1, 3),       # matrix-core kernel, 1 k-step, more than 64 time steps
+    (3, 77, 3, 64),       # wavefront kernel, every lane owns a component; N not a multiple of the 8 wavefronts
+    (1, 9, 2, 2),         # matrix-core kernel, a single time step: no backward pass
     (5, 203, 2, 17),      # matrix-core kernel, 5 k-steps with three padded components, 2 column tiles
-    (4, 100, 3, 33),      # 9 k-steps, 3 column tiles
-    (6, 45, 2, 7),        # 2 k-steps, one column tile
-    (12, 16, 4, 48),      # 12 k-steps, exactly one group of 16 nodes
+    (4, 100, 3, 33),      # K > 32: wavefront kernel, transition matrices in LDS, 5 trips of 8 components
+    (6, 45, 2, 7),        # matrix-core kernel, 2 k-steps, one column tile
+    (12, 16, 4, 48),      # K > 32: wavefront kernel, matrices in global memory, two workgroups of 8 nodes
 ])
 def test_labels_shapes_against_oracle(eng, T, N, D, K):
     rng = np.random.RandomState(T * 131 + K)
