@@ -165,6 +165,9 @@ SIGNATURES = {
     'dlsm_gof_dynamic_simulate': (C.c_int, [handle_t, c_double_p, c_double_p, c_double_p, C.c_int, C.c_uint64,
                                             C.c_uint32, C.c_int, c_i64_p, c_i64_p, c_i64_p, c_u32_p]),
     'dlsm_gof_dynamic_observed': (C.c_int, [handle_t, c_u32_p, c_i64_p, c_i64_p, c_i64_p]),
+    'dlsm_gof_triads_simulate': (C.c_int, [handle_t, c_double_p, c_double_p, c_double_p, C.c_int, C.c_uint64,
+                                           C.c_uint32, C.c_int, c_i64_p, c_u32_p]),
+    'dlsm_gof_triads_observed': (C.c_int, [handle_t, c_u32_p, c_i64_p]),
     'dlsm_ic_accumulate': (C.c_int, [handle_t, c_u32_p, c_double_p, c_double_p, c_double_p, C.c_int,
                                      c_double_p, c_double_p, c_double_p]),
     'dlsm_score_accumulate': (C.c_int, [handle_t, c_u32_p, c_u32_p, c_double_p, c_double_p, c_double_p, C.c_int,

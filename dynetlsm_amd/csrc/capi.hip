@@ -33,6 +33,7 @@
 #include "kernels_forecast_paths.hpp"
 #include "kernels_gof.hpp"
 #include "kernels_gof_dynamic.hpp"
+#include "kernels_gof_triads.hpp"
 #include "kernels_dyad_pass.hpp"
 #include "kernels_ic.hpp"
 #include "kernels_score.hpp"
@@ -2132,6 +2133,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_samples.hpp"
 #include "capi_gof.hpp"
 #include "capi_gof_dynamic.hpp"
+#include "capi_gof_triads.hpp"
 #include "capi_ic.hpp"
 #include "capi_score.hpp"
 #include "capi_conv.hpp"

@@ -25,23 +25,32 @@ int gof_stats_launch(dlsm_chain *h, const uint32_t *rows, const uint32_t *trows,
     return DLSM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dlsm_gof_simulate(dlsm_chain *h, const double *Xs, const double *intercepts, const double *radii, int S,
-                      uint64_t seed, uint32_t first_index, int batch, int64_t *stats, uint32_t *bits) {
-    NEED(h, h && Xs && intercepts && stats, "null argument");
-    const bool directed = h->model != DLSM_UNDIRECTED;
-    NEED(h, !directed || radii, "directed models need the radii");
+// the checks of the arguments every *_simulate entry point takes (after its own null checks)
+int gof_simulate_check(dlsm_chain *h, const double *radii, int S, uint32_t first_index, int batch) {
+    NEED(h, h->model == DLSM_UNDIRECTED || radii, "directed models need the radii");
     NEED(h, S >= 1, "needs at least one sample");
     NEED(h, batch >= 0, "batch must be >= 0 (0: automatic)");
     NEED(h, (uint64_t)first_index + (uint64_t)S <= ((uint64_t)1 << 32), "first_index + S must be <= 2^32");
+    return DLSM_OK;
+}
+
+// The batch loop of every *_simulate entry point.  The S samples go to the device `nb` at a time: `batch`,
+// or as many as GOF_SCRATCH_BYTES hold of networks, positions and `record_entries` int64 of records per
+// sample, and no more than the grid's y extent holds networks.  Per batch of n samples from sample s0:
+// upload, draw the n * T networks (k_gof_draw: a function of seed, first_index + s and t alone), enqueue
+// the copy of the rows to `bits` (if given), then `stats(rows, trows, n, s0, drec)` - rows and (directed,
+// else NULL) transposed rows [n * T][N][W] and drec, nb * record_entries int64, all on the device - which
+// launches the statistics, copies them to the caller and returns with the stream synchronised.
+template <class Stats>
+int gof_simulate_batches(dlsm_chain *h, const double *Xs, const double *intercepts, const double *radii, int S,
+                         uint64_t seed, uint32_t first_index, int batch, size_t record_entries, uint32_t *bits,
+                         Stats &&stats) {
+    const bool directed = h->model != DLSM_UNDIRECTED;
     HIPCHK(h, hipSetDevice(h->device));
     const int T = h->T, N = h->N, D = h->D, W = h->W;
-    const size_t R = 2 + 3 * (size_t)N, net_words = (size_t)N * W, nmat = directed ? 2 : 1;
-    const size_t per_sample = (size_t)T * (net_words * nmat * sizeof(uint32_t) + R * sizeof(int64_t) +
-                                           (size_t)N * D * sizeof(double));
+    const size_t net_words = (size_t)N * W, nmat = directed ? 2 : 1;
+    const size_t per_sample = (size_t)T * (net_words * nmat * sizeof(uint32_t) + (size_t)N * D * sizeof(double)) +
+                              record_entries * sizeof(int64_t);
     int nb = batch > 0 ? batch : (int)std::max<size_t>(1, GOF_SCRATCH_BYTES / per_sample);
     nb = std::min(nb, S);
     nb = std::min(nb, std::max(1, 65535 / T));          // networks of a batch: the grid's y extent
@@ -49,7 +58,7 @@ int dlsm_gof_simulate(dlsm_chain *h, const double *Xs, const double *intercepts,
     DevArray<int64_t> bS;
     if (bX.alloc(h, (size_t)nb * T * N * D) || bB.alloc(h, (size_t)nb * 2) ||
         (directed && bR.alloc(h, (size_t)nb * N)) || bBits.alloc(h, (size_t)nb * T * net_words * nmat) ||
-        bS.alloc(h, (size_t)nb * T * R)) return DLSM_E_HIP;
+        bS.alloc(h, (size_t)nb * record_entries)) return DLSM_E_HIP;
     const unsigned gx = (unsigned)((net_words + 255) / 256);
     for (int s0 = 0; s0 < S; s0 += nb) {
         const int n = std::min(nb, S - s0), nets = n * T;
@@ -66,18 +75,34 @@ int dlsm_gof_simulate(dlsm_chain *h, const double *Xs, const double *intercepts,
                                             seed, first_index + (uint32_t)s0, bBits));
         HIPCHK(h, hipGetLastError());
         const uint32_t *rows = bBits;
-        int rc = gof_stats_launch(h, rows, directed ? rows + (size_t)nets * net_words : nullptr, nets,
-                                  bS);
-        if (rc) return rc;
-        HIPCHK(h, hipMemcpyAsync(stats + (size_t)s0 * T * R, bS, (size_t)nets * R * sizeof(int64_t),
-                                 hipMemcpyDeviceToHost, h->stream));
         if (bits)
             HIPCHK(h, hipMemcpyAsync(bits + (size_t)s0 * T * net_words, rows,
                                      (size_t)nets * net_words * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                      h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (int rc = stats(rows, directed ? rows + (size_t)nets * net_words : nullptr, n, (size_t)s0, bS.get()))
+            return rc;
     }
     return DLSM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dlsm_gof_simulate(dlsm_chain *h, const double *Xs, const double *intercepts, const double *radii, int S,
+                      uint64_t seed, uint32_t first_index, int batch, int64_t *stats, uint32_t *bits) {
+    NEED(h, h && Xs && intercepts && stats, "null argument");
+    if (int rc = gof_simulate_check(h, radii, S, first_index, batch)) return rc;
+    const size_t R = 2 + 3 * (size_t)h->N, TR = (size_t)h->T * R;
+    return gof_simulate_batches(h, Xs, intercepts, radii, S, seed, first_index, batch, TR, bits,
+                                [&](const uint32_t *rows, const uint32_t *trows, int n, size_t s0,
+                                    int64_t *drec) -> int {
+        if (int rc = gof_stats_launch(h, rows, trows, n * h->T, drec)) return rc;
+        HIPCHK(h, hipMemcpyAsync(stats + s0 * TR, drec, (size_t)n * TR * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                 h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return DLSM_OK;
+    });
 }
 
 int dlsm_gof_observed(dlsm_chain *h, const uint32_t *bits, int64_t *stats) {

@@ -99,54 +99,15 @@ int dlsm_gof_dynamic_simulate(dlsm_chain *h, const double *Xs, const double *int
     const bool temporal = overlap != nullptr, geo = geodesic != nullptr;
     NEED(h, temporal || geo, "overlap and steps, or geodesic, or both must be given");
     NEED(h, temporal == (steps != nullptr) || h->T == 1, "overlap and steps go together");
-    const bool directed = h->model != DLSM_UNDIRECTED;
-    NEED(h, !directed || radii, "directed models need the radii");
-    NEED(h, S >= 1, "needs at least one sample");
-    NEED(h, batch >= 0, "batch must be >= 0 (0: automatic)");
-    NEED(h, (uint64_t)first_index + (uint64_t)S <= ((uint64_t)1 << 32), "first_index + S must be <= 2^32");
-    int rc = gof_dynamic_check(h, geo);
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int T = h->T, N = h->N, D = h->D, W = h->W;
-    const GofDynSizes sz(T, N, temporal, geo);
-    const size_t net_words = (size_t)N * W, nmat = directed ? 2 : 1;
-    const size_t per_sample = (size_t)T * (net_words * nmat * sizeof(uint32_t) + (size_t)N * D * sizeof(double)) +
-                              sz.total() * sizeof(int64_t);
-    int nb = batch > 0 ? batch : (int)std::max<size_t>(1, GOF_SCRATCH_BYTES / per_sample);
-    nb = std::min(nb, S);
-    nb = std::min(nb, std::max(1, 65535 / T));          // networks of a batch: the grid's y extent
-    DevArray<double> bX, bB, bR; DevArray<uint32_t> bBits;
-    DevArray<int64_t> bS;
-    if (bX.alloc(h, (size_t)nb * T * N * D) || bB.alloc(h, (size_t)nb * 2) ||
-        (directed && bR.alloc(h, (size_t)nb * N)) || bBits.alloc(h, (size_t)nb * T * net_words * nmat) ||
-        bS.alloc(h, (size_t)nb * sz.total())) return DLSM_E_HIP;
-    const unsigned gx = (unsigned)((net_words + 255) / 256);
-    for (int s0 = 0; s0 < S; s0 += nb) {
-        const int n = std::min(nb, S - s0), nets = n * T;
-        HIPCHK(h, hipMemcpyAsync(bX, Xs + (size_t)s0 * T * N * D, (size_t)nets * N * D * sizeof(double),
-                                 hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(bB, intercepts + 2 * (size_t)s0, (size_t)n * 2 * sizeof(double),
-                                 hipMemcpyHostToDevice, h->stream));
-        if (directed)
-            HIPCHK(h, hipMemcpyAsync(bR, radii + (size_t)s0 * N, (size_t)n * N * sizeof(double),
-                                     hipMemcpyHostToDevice, h->stream));
-        DISPATCH_D(h, D, hipLaunchKernelGGL((k_gof_draw<DD>), dim3(gx, nets, (unsigned)nmat), dim3(256), 0,
-                                            h->stream, bX, bB,
-                                            directed ? bR.get() : nullptr, T, N, W, (int)directed,
-                                            seed, first_index + (uint32_t)s0, bBits));
-        HIPCHK(h, hipGetLastError());
-        const uint32_t *rows = bBits;
-        rc = gof_dynamic_launch(h, rows, directed ? rows + (size_t)nets * net_words : nullptr, n, temporal, geo,
-                                bS);
-        if (rc) return rc;
-        if (bits)
-            HIPCHK(h, hipMemcpyAsync(bits + (size_t)s0 * T * net_words, rows,
-                                     (size_t)nets * net_words * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                     h->stream));
-        rc = gof_dynamic_fetch(h, bS, n, (size_t)s0, temporal, geo, overlap, steps, geodesic);
-        if (rc) return rc;
-    }
-    return DLSM_OK;
+    int rc = gof_simulate_check(h, radii, S, first_index, batch);
+    if (rc || (rc = gof_dynamic_check(h, geo))) return rc;
+    const GofDynSizes sz(h->T, h->N, temporal, geo);
+    return gof_simulate_batches(h, Xs, intercepts, radii, S, seed, first_index, batch, sz.total(), bits,
+                                [&](const uint32_t *rows, const uint32_t *trows, int n, size_t s0,
+                                    int64_t *drec) -> int {
+        if (int rc = gof_dynamic_launch(h, rows, trows, n, temporal, geo, drec)) return rc;
+        return gof_dynamic_fetch(h, drec, n, s0, temporal, geo, overlap, steps, geodesic);
+    });
 }
 
 int dlsm_gof_dynamic_observed(dlsm_chain *h, const uint32_t *bits, int64_t *overlap, int64_t *steps,

@@ -869,6 +869,30 @@ class Chain(object):
             _p(st) if temporal else None, _p(geo) if geodesic else None))
         return ov, st, geo
 
+    TRIAD_RECORD_LENGTH = 51
+
+    def gof_triads_simulate(self, Xs, intercepts, radii=None, seed=0, first_index=0, batch=0, want_bits=False):
+        """The triad records (S, T, 51) int64 of the networks ``gof_simulate`` draws for the same arguments,
+        ``seed`` and ``first_index`` (csrc/kernels_gof_triads.hpp; layout in include/dynetlsm_hip.h:
+        [(c - 1) * 16 + a * 4 + b] over the connected pairs of dyad code c, then the three pair counts).
+        ``want_bits``: also the drawn rows (S, T, N, W) uint32."""
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii, min_samples=0)
+        triads = np.zeros((S, self.T, self.TRIAD_RECORD_LENGTH), dtype=np.int64)
+        W = packed_row_words(self.N)
+        bits = np.zeros((S, self.T, self.N, W), dtype=np.uint32) if want_bits else None
+        self._ck(self._L.dlsm_gof_triads_simulate(
+            self._h, _p(Xs), _p(b), _p(r) if r is not None else None, int(S),
+            C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(first_index)), int(batch), _p(triads),
+            bits.ctypes.data_as(_lib.c_u32_p) if want_bits else None))
+        return (triads, bits) if want_bits else triads
+
+    def gof_triads_observed(self, bits):
+        """triad records (T, 51) int64 of the packed network ``bits`` (T, N, W) uint32 (``pack_network``)"""
+        bits = self._packed(bits, 'bits')
+        triads = np.zeros((self.T, self.TRIAD_RECORD_LENGTH), dtype=np.int64)
+        self._ck(self._L.dlsm_gof_triads_observed(self._h, bits.ctypes.data_as(_lib.c_u32_p), _p(triads)))
+        return triads
+
     # -- information criteria (no reference counterpart) ---------------------------------------
     def ic_accumulate(self, bits, Xs, intercepts, radii=None, want_pointwise=False):
         """Pointwise log-likelihood of the packed network ``bits`` (T, N, W) uint32 (``pack_network``)

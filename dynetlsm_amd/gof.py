@@ -13,7 +13,16 @@ Two further families look at what makes the model dynamic and at structure beyon
 dissolved, the persistence-degree histogram and the shared partners of newly formed ties - and
 ``statistics='geodesic'`` - the distribution of shortest-path lengths.  The draws at t and t + 1
 are independent given the positions, so all persistence of ties comes from persistence of positions.
+
+A fourth family, ``statistics='triadic'``, is the triad census (``Chain.gof_triads_simulate``,
+``Chain.gof_triads_observed``: csrc/kernels_gof_triads.hpp): the 16 Holland-Leinhardt MAN classes of a
+directed network - sna's ``triad.census``, ergm's ``triadcensus`` term - or the four of an undirected one,
+with the dyad census, the transitive triples and the two-paths.  The device counts, per connected pair, the
+third nodes in each of their 16 states; the host maps those states to the classes by a table it derives
+from one representative per class.
 """
+import itertools
+
 import numpy as np
 
 from ._trace import model_chain, observed_network, sample_rows, trace_samples
@@ -21,9 +30,11 @@ from .engine import pack_network
 from .lsm import check_random_state
 
 __all__ = ['posterior_predictive_check', 'GofResult', 'derive_statistics', 'mc_p_values',
-           'network_statistics_from_records', 'derive_dynamic_statistics', 'FAMILIES']
+           'network_statistics_from_records', 'derive_dynamic_statistics', 'FAMILIES',
+           'derive_triad_statistics', 'TRIAD_NAMES', 'UNDIRECTED_TRIAD_NAMES']
 
-FAMILIES = ('structural', 'temporal', 'geodesic')
+FAMILIES = ('structural', 'temporal', 'geodesic')       # what 'all' means
+TRIADIC = 'triadic'                                     # asked for by name
 
 
 def network_statistics_from_records(stats, N, is_directed):
@@ -112,6 +123,77 @@ def derive_dynamic_statistics(overlap, steps, geodesic, edges, N, is_directed):
     return out
 
 
+# One representative per MAN class, in the standard order (the convention of sna and networkx), as arcs on
+# the nodes A, B, C.  Everything else about the classes is derived from these below.
+_TRIAD_REPRESENTATIVES = (
+    ('003', ''), ('012', 'AB'), ('102', 'AB BA'), ('021D', 'BA BC'), ('021U', 'AB CB'), ('021C', 'AB BC'),
+    ('111D', 'AB BA CB'), ('111U', 'AB BA BC'), ('030T', 'AB CB AC'), ('030C', 'BA CB AC'),
+    ('201', 'AB BA BC CB'), ('120D', 'BA BC AC CA'), ('120U', 'AB CB AC CA'), ('120C', 'AB BC AC CA'),
+    ('210', 'AB BC CB AC CA'), ('300', 'AB BA BC CB AC CA'))
+TRIAD_NAMES = tuple(name for name, _ in _TRIAD_REPRESENTATIVES)
+UNDIRECTED_TRIAD_NAMES = ('empty', 'edge', 'path', 'triangle')
+_UNDIRECTED_CLASSES = tuple(TRIAD_NAMES.index(n) for n in ('003', '102', '201', '300'))
+
+
+def _derive_triad_tables():
+    """From the representatives: ``table`` (4, 4, 4), the class of the labelled triad on (i, j, k) with the
+    dyad codes c of (i, j), a of (i, k) and b of (j, k) - code = arc from the first to the second node + 2 x
+    the arc back -, and per class the non-null dyads, the transitive triples (ordered x -> y -> z with
+    x -> z) and the two-paths (ordered x -> y -> z, x != z)"""
+    nodes = (0, 1, 2)
+    perms = list(itertools.permutations(nodes))
+
+    def canonical(arcs):
+        return min(tuple(sorted((p[x], p[y]) for x, y in arcs)) for p in perms)
+
+    reps = [frozenset(('ABC'.index(a[0]), 'ABC'.index(a[1])) for a in arcs.split())
+            for _, arcs in _TRIAD_REPRESENTATIVES]
+    class_of = {canonical(arcs): k for k, arcs in enumerate(reps)}
+    assert len(class_of) == len(reps)
+    table = np.zeros((4, 4, 4), dtype=np.int64)
+    for c, a, b in itertools.product(range(4), repeat=3):
+        arcs = set()
+        for code, (x, y) in ((c, (0, 1)), (a, (0, 2)), (b, (1, 2))):
+            if code & 1:
+                arcs.add((x, y))
+            if code & 2:
+                arcs.add((y, x))
+        table[c, a, b] = class_of[canonical(arcs)]
+    dyads = np.array([sum(1 for x, y in ((0, 1), (0, 2), (1, 2)) if (x, y) in r or (y, x) in r) for r in reps])
+    paths = np.array([sum(1 for x, y, z in perms if (x, y) in r and (y, z) in r) for r in reps])
+    trans = np.array([sum(1 for x, y, z in perms if (x, y) in r and (y, z) in r and (x, z) in r) for r in reps])
+    return table, dyads, trans, paths
+
+
+TRIAD_TABLE, TRIAD_DYADS, TRIAD_TRANSITIVE, TRIAD_TWO_PATHS = _derive_triad_tables()
+
+
+def derive_triad_statistics(records, N, is_directed):
+    """The named statistics of triad records (..., 51) (layout: include/dynetlsm_hip.h,
+    dlsm_gof_triads_simulate): 'triad_census' (..., 16) in the order of ``TRIAD_NAMES``, or (..., 4)
+    undirected - ``UNDIRECTED_TRIAD_NAMES``, the classes 003, 102, 201 and 300 -; 'dyad_census' (..., 3),
+    mutual, asymmetric and null pairs; 'transitive_triples', the ordered (i, j, k) with i -> j, j -> k and
+    i -> k; 'two_paths', i -> j -> k with i != k; 'triad_transitivity', their ratio (0 without two-paths;
+    undirected, the structural family's 'transitivity').
+
+    The records count every triad once per non-null dyad of it, so each class's sum of states is divided
+    by that number; class 003, which no connected pair sees, is C(N, 3) minus the rest."""
+    records = np.asarray(records, dtype=np.int64)
+    states = records[..., :48].reshape(records.shape[:-1] + (3, 16))
+    visits = np.zeros(records.shape[:-1] + (16,), dtype=np.int64)
+    for c in (1, 2, 3):
+        for k in range(1, 16):
+            visits[..., k] += states[..., c - 1, TRIAD_TABLE[c].ravel() == k].sum(-1)
+    census = visits // np.maximum(TRIAD_DYADS, 1)
+    census[..., 0] = N * (N - 1) * (N - 2) // 6 - census[..., 1:].sum(-1)
+    mutual, asym = records[..., 50], records[..., 48] + records[..., 49]
+    dyad = np.stack([mutual, asym, N * (N - 1) // 2 - mutual - asym], axis=-1)
+    trans, paths = census @ TRIAD_TRANSITIVE, census @ TRIAD_TWO_PATHS
+    return {'triad_census': census if is_directed else census[..., list(_UNDIRECTED_CLASSES)],
+            'dyad_census': dyad, 'transitive_triples': trans, 'two_paths': paths,
+            'triad_transitivity': _ratio(trans, paths)}
+
+
 def mc_p_values(simulated, observed):
     """Two-sided Monte Carlo p-value per entry: min(1, 2 min(P(sim >= obs), P(sim <= obs))) over the
     first axis of ``simulated``"""
@@ -134,6 +216,9 @@ class GofResult(object):
     'overlap' (T, T); 'persisted', 'formed', 'dissolved', 'persistence' (T - 1,) per step; 'stability'
     (T - 1,) per lag; 'persist_degree', 'formed_sp' (T - 1, N); 'geodesic' (T, N); 'unreachable',
     'mean_geodesic', 'diameter' (T,) - simulated with a leading S.
+
+    With the triadic family (``derive_triad_statistics``): 'triad_census' (T, 16) or, undirected, (T, 4);
+    'dyad_census' (T, 3); 'transitive_triples', 'two_paths', 'triad_transitivity' (T,).
     """
     HIST = ('degree', 'out_degree', 'in_degree', 'esp')
 
@@ -170,6 +255,11 @@ class GofResult(object):
             if 'geodesic' in d:
                 out['geodesic'] = d['geodesic'].sum(axis=axis)
                 out['unreachable'] = d['unreachable'].sum(axis=axis)
+            if 'triad_census' in d:
+                # counts summed, the ratio from the pooled counts
+                for name in ('triad_census', 'dyad_census', 'transitive_triples', 'two_paths'):
+                    out[name] = d[name].sum(axis=axis)
+                out['triad_transitivity'] = _ratio(out['transitive_triples'], out['two_paths'])
             return out
         return pool(self.observed, 0), pool(self.simulated, 1)
 
@@ -205,6 +295,10 @@ class GofResult(object):
             for k in range(1, int(nz[-1]) + 2 if nz.size else 1):
                 row('geodesic[%d]' % k, obs['geodesic'][k], sim['geodesic'][:, k])
             row('unreachable', obs['unreachable'], sim['unreachable'])
+        if 'triad_census' in obs:
+            for k, name in enumerate(TRIAD_NAMES if self.is_directed else UNDIRECTED_TRIAD_NAMES):
+                row('triad[%s]' % name, obs['triad_census'][k], sim['triad_census'][:, k])
+            row('triad_transitivity', obs['triad_transitivity'], sim['triad_transitivity'])
         return '\n'.join(lines)
 
     def __repr__(self):
@@ -212,8 +306,9 @@ class GofResult(object):
 
 
 def _families(statistics):
-    """'structural' | 'temporal' | 'geodesic' | 'all' | a tuple of the first three -> the tuple, in
-    the order of FAMILIES"""
+    """'structural' | 'temporal' | 'geodesic' | 'triadic' | 'all' (the first three) | a tuple of the first
+    four -> the tuple, in the order of FAMILIES with 'triadic' last"""
+    known = FAMILIES + (TRIADIC,)
     if isinstance(statistics, str):
         names = FAMILIES if statistics == 'all' else (statistics,)
     else:
@@ -221,11 +316,11 @@ def _families(statistics):
             names = tuple(statistics)
         except TypeError:
             names = (statistics,)
-    bad = [n for n in names if n not in FAMILIES]
+    bad = [n for n in names if n not in known]
     if bad or not names:
-        raise ValueError("statistics must be 'structural', 'temporal', 'geodesic', 'all' or a tuple of the "
-                         "first three, got %r" % (statistics,))
-    return tuple(f for f in FAMILIES if f in names)
+        raise ValueError("statistics must be 'structural', 'temporal', 'geodesic', 'triadic', 'all' (the first "
+                         "three) or a tuple of the first four, got %r" % (statistics,))
+    return tuple(f for f in known if f in names)
 
 
 def posterior_predictive_check(model, n_samples=100, random_state=None, statistics='structural'):
@@ -242,9 +337,10 @@ def posterior_predictive_check(model, n_samples=100, random_state=None, statisti
 
     ``statistics`` chooses the families: 'structural' (the default: the statistics above, one time step
     at a time), 'temporal' (tie persistence from one step to the next; needs T >= 2), 'geodesic' (the
-    shortest-path lengths: about N^2 W row-word reads per network, the slowest family), 'all', or a tuple
-    of the first three.  The seed does not depend on it: every family of one ``random_state`` describes
-    the same drawn networks.
+    shortest-path lengths: about N^2 W row-word reads per network, the slowest family), 'triadic' (the
+    triad census - 16 MAN classes directed, four undirected -, the dyad census, transitive triples and
+    two-paths), 'all' (the first three), or a tuple of the first four.  The seed does not depend on it:
+    every family of one ``random_state`` describes the same drawn networks.
 
     Returns a ``GofResult``.
     """
@@ -272,7 +368,13 @@ def posterior_predictive_check(model, n_samples=100, random_state=None, statisti
             obs_rec = chain.gof_dynamic_observed(bits, temporal=temporal, geodesic=geodesic)
             sim_rec = chain.gof_dynamic_simulate(Xs, ic, radii, seed=seed, temporal=temporal,
                                                  geodesic=geodesic)
+        if TRIADIC in families:
+            obs_tri = chain.gof_triads_observed(bits)
+            sim_tri = chain.gof_triads_simulate(Xs, ic, radii, seed=seed)
     if temporal or geodesic:
         observed.update(derive_dynamic_statistics(*obs_rec, None, N, directed))
         simulated.update(derive_dynamic_statistics(*sim_rec, None, N, directed))
+    if TRIADIC in families:
+        observed.update(derive_triad_statistics(obs_tri, N, directed))
+        simulated.update(derive_triad_statistics(sim_tri, N, directed))
     return GofResult(ids, observed, simulated, directed, N)

@@ -424,6 +424,22 @@ int dlsm_gof_dynamic_simulate(dlsm_chain *h, const double *Xs, const double *int
  * dlsm_gof_observed validates it. */
 int dlsm_gof_dynamic_observed(dlsm_chain *h, const uint32_t *bits, int64_t *overlap, int64_t *steps,
                               int64_t *geodesic);
+/* triad census of the same draws (no reference counterpart; the statistic of sna's triad.census and ergm's
+ * triadcensus term).  A record of 51 int64 per (sample, t), summed over the connected pairs i < j - those
+ * with at least one arc between them - of dyad code c = Y[i,j] + 2 Y[j,i] in {1, 2, 3}:
+ *   [(c - 1) * 16 + a * 4 + b]  third nodes k (not i, not j) with a = Y[i,k] + 2 Y[k,i] and
+ *                               b = Y[j,k] + 2 Y[k,j], a, b = 0..3
+ *   [48 + c - 1]                connected pairs of code c
+ * Undirected handles: only c = 3 and a, b in {0, 3} occur.  A triad with m non-null dyads is counted m
+ * times; the host maps (c, a, b) to the 16 MAN classes and gets class 003 by subtraction from C(N, 3)
+ * (dynetlsm_amd/gof.py).  triads S*T*51; every other argument, check, the batching and the RNG indexing are
+ * those of dlsm_gof_simulate: the same seed and first_index draw the same networks. */
+int dlsm_gof_triads_simulate(dlsm_chain *h, const double *Xs, const double *intercepts, const double *radii,
+                             int S, uint64_t seed, uint32_t first_index, int batch, int64_t *triads,
+                             uint32_t *bits);
+/* the same records of a packed network `bits` T*N*W uint32 supplied by the caller, validated as
+ * dlsm_gof_observed validates it; triads T*51 int64. */
+int dlsm_gof_triads_observed(dlsm_chain *h, const uint32_t *bits, int64_t *triads);
 
 /* ---- information criteria (WAIC, DIC) ----------------------------------- */
 /* No reference counterpart.  The pointwise log-likelihood l_s = y eta_s - log(1 + exp(eta_s)) of every
