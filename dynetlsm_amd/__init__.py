@@ -20,7 +20,7 @@ from .scores import in_sample_scores, ScoreResult  # noqa
 from .convergence import convergence_diagnostics, ConvergenceResult  # noqa
 from .probabilities import edge_probabilities, EdgeProbabilityResult  # noqa
 from . import ranking  # noqa
-from .ranking import top_dyads, TopDyadsResult  # noqa
+from .ranking import top_dyads, TopDyadsResult, top_partners, TopPartnersResult  # noqa
 from . import dynamics  # noqa
 from .dynamics import tie_dynamics, TieDynamicsResult  # noqa
 from . import community  # noqa
@@ -36,4 +36,4 @@ __all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
            'in_sample_scores', 'ScoreResult', 'convergence_diagnostics', 'ConvergenceResult', 'forecast',
            'ForecastResult', 'edge_probabilities', 'EdgeProbabilityResult', 'dynamics', 'tie_dynamics',
            'TieDynamicsResult', 'community', 'community_structure', 'CommunityResult', 'ranking', 'top_dyads',
-           'TopDyadsResult']
+           'TopDyadsResult', 'top_partners', 'TopPartnersResult']

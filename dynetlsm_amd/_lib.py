@@ -21,7 +21,7 @@ handle_t = C.c_void_p
 
 (K_LOGLIK, K_SWEEP, K_CENTER, K_LABELS, K_FINALIZE, K_SWEEP_EVAL, K_SWEEP_RESOLVE,
  K_INIT, K_HDP_TAIL, K_SCORE_ACCUMULATE, K_SCORE_CLEAR, K_SCORE_SCAN,
- K_TOPK_COUNT, K_TOPK_SCAN, K_TOPK_EMIT) = range(15)
+ K_TOPK_COUNT, K_TOPK_SCAN, K_TOPK_EMIT, K_PARTNERS) = range(16)
 UNDIRECTED, DIRECTED, DIRECTED_CASE_CONTROL = 0, 1, 2
 
 
@@ -184,6 +184,9 @@ SIGNATURES = {
                                            C.c_int, C.c_int, c_u64_p, c_u64_p, c_u64_p, c_u64_p, c_double_p]),
     'dlsm_topk_accumulate': (C.c_int, [handle_t, c_u32_p, c_u32_p, c_double_p, c_double_p, c_double_p, C.c_int,
                                        C.c_int, C.c_int, C.c_int64, C.c_int64, c_i32_p, c_double_p, c_i32_p, c_i64_p]),
+    'dlsm_partners_accumulate': (C.c_int, [handle_t, c_u32_p, c_u32_p, c_double_p, c_double_p, c_double_p, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, c_i32_p, C.c_int, c_i32_p, c_double_p, c_i32_p,
+                                           c_i32_p]),
     'dlsm_community_accumulate': (C.c_int, [handle_t, c_u32_p, c_u32_p, c_i64_p, C.c_int, C.c_int, C.c_int, c_i64_p,
                                             c_i64_p, c_i64_p, c_i64_p, c_i64_p]),
     'dlsm_forecast_paths': (C.c_int, [handle_t, c_double_p, c_double_p, c_double_p, c_i32_p, c_double_p, c_double_p,

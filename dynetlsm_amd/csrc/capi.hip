@@ -2141,6 +2141,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 #include "capi_proba.hpp"
 #include "capi_dynamics.hpp"
 #include "capi_topk.hpp"
+#include "capi_partners.hpp"
 #include "capi_community.hpp"
 #include "capi_forecast_paths.hpp"
 #include "capi_hdp.hpp"

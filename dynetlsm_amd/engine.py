@@ -56,6 +56,17 @@ def rank_candidates(index, value, k, largest=True):
             np.ascontiguousarray(value[:, 0]), np.ascontiguousarray(value[:, 1]))
 
 
+def check_node_ids(nodes, N, name='nodes'):
+    """a non-empty one-dimensional array of integer node ids in 0..N-1 as int64 (ValueError, before any device
+    call)"""
+    ids = np.asarray(nodes)
+    if ids.ndim != 1 or not ids.size or ids.dtype == bool or not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError('%s must be a non-empty one-dimensional array of integer node ids, got %r' % (name, nodes))
+    if (ids < 0).any() or (ids >= N).any():
+        raise ValueError('%s must lie in 0..%d, got %r' % (name, N - 1, nodes))
+    return ids.astype(np.int64)
+
+
 def check_missing_index(index, T, N, model):
     """(n, 3) int32 rows (t, i, j) of missing dyads, validated as ``dlsm_set_missing`` validates them
     (ValueError, before any device call)"""
@@ -1087,6 +1098,57 @@ class Chain(object):
             n_tiles = sum(1 for bi in range(n_rb) for bj in range(n_cb) if bi * tile_rows < min(N, (bj + 1) * 64) - 1)
         return steps, dict(eligible=diag[:, 0].copy(), n_beyond=diag[:, 1].copy(), n_at=diag[:, 2].copy(),
                            key=diag[:, 3].copy(), tiles_revisited=diag[:, 4].copy(), n_tiles=n_tiles)
+
+    # -- per-node link prediction (no reference counterpart) ----------------------------------------
+    PARTNERS_K_MAX = 64
+
+    def partners_accumulate(self, bits, Xs, intercepts, radii, k, among='non_ties', largest=True, mask=None,
+                            rows=None):
+        """For every time step and every node i the ``k`` <= 64 eligible partners j != i that come first by the
+        posterior-mean edge probability of the dyad (i, j) over the S >= 2 samples (arguments and ``among`` as
+        ``topk_accumulate``): probability descending - ``largest=False``: ascending -, then j.  Directed chains rank
+        the receivers j of sender i; undirected chains read the network and the mask of {i, j} as ``topk_accumulate``
+        does.  Each row's list is kept on the device while its columns stream by (csrc/kernels_partners.hpp; the
+        definition: include/dynetlsm_hip.h): no (T, N, N) array is formed.  ``rows``: node ids; only the row blocks
+        that hold them are computed, and every row that was not asked for comes back as padding.  Returns ``partner``
+        (T, N, k) int64, padded with -1, ``proba`` and ``sd`` (T, N, k), padded with NaN, ``y`` (T, N, k) int64, the
+        partners' bits of the network, padded with -1, and ``eligible`` (T, N) int64, the eligible partners of each
+        row: -1 for the rows of blocks that were not computed."""
+        if among not in self.TOPK_AMONG:
+            raise ValueError('among must be one of %s, got %r' % (', '.join(map(repr, self.TOPK_AMONG)), among))
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= self.PARTNERS_K_MAX:
+            raise ValueError('k must be an integer in 1..%d, the entries of a node\'s list, got %r'
+                             % (self.PARTNERS_K_MAX, k))
+        k = int(k)
+        bits = self._packed(bits, 'bits')
+        if mask is not None:
+            mask = self._packed(mask, 'mask')
+        elif among == 'missing':
+            raise ValueError("among='missing' needs the mask of the missing dyads")
+        if np.shape(Xs)[0] < 2:
+            raise ValueError('needs at least two samples (the standard deviation has ddof = 1)')
+        Xs, b, r, S = self._sample_args(Xs, intercepts, radii)
+        T, N = self.T, self.N
+        blocks = None
+        if rows is not None:
+            rows = np.unique(check_node_ids(rows, N, 'rows'))
+            blocks = np.ascontiguousarray(np.unique(rows // (32 if self.D <= 4 else 16)), dtype=np.int32)
+        partner = np.zeros((T, N, k), dtype=np.int32)
+        value = np.zeros((T, N, k, 2))
+        y = np.zeros((T, N, k), dtype=np.int32)
+        eligible = np.zeros((T, N), dtype=np.int32)
+        self._ck(self._L.dlsm_partners_accumulate(
+            self._h, _p(bits), _po(mask), _p(Xs), _p(b), _po(r), int(S), self.TOPK_AMONG.index(among),
+            int(bool(largest)), k, _po(blocks), 0 if blocks is None else int(blocks.size), _p(partner), _p(value),
+            _p(y), _p(eligible)))
+        if rows is not None:
+            # rows that share a block with an asked row were computed: they are padding all the same
+            drop = np.ones(N, dtype=bool)
+            drop[rows] = False
+            partner[:, drop], y[:, drop], value[:, drop] = -1, -1, np.nan
+            eligible[:, drop] = -1
+        return (partner.astype(np.int64), np.ascontiguousarray(value[..., 0]), np.ascontiguousarray(value[..., 1]),
+                y.astype(np.int64), eligible.astype(np.int64))
 
     # -- tie dynamics (no reference counterpart) ---------------------------------------------------
     def dynamics_accumulate(self, bits, Xs, intercepts, radii, min_count, mask=None, n_bins=20, pointwise=False):

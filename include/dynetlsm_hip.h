@@ -635,6 +635,30 @@ int dlsm_topk_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *ma
                          int64_t max_candidates, int32_t *cand_index, double *cand_value, int32_t *n_cand,
                          int64_t *diag);
 
+/* ---- per-node link prediction (each node's top-k partners) ---------------- */
+/* No reference counterpart.  For every time step t and every node i of the listed row blocks, over the eligible
+ * partners j != i (`among`, `mask`, pbar, sd, y and the samples as dlsm_topk_accumulate; 2 <= S), the k first in the
+ * order (pbar(t, i, j) descending, j ascending; largest = 0: pbar ascending, j ascending), 1 <= k <= 64.  Directed and
+ * case-control handles rank the receivers j of sender i by p(i -> j); the senders of a receiver are ranked by the same
+ * call on the transposed network and mask with the two intercept columns swapped.  Undirected handles visit both
+ * triangles (about N*N dyad evaluations per sample and time step); the bit of the network and of the mask of {i, j} are
+ * those of (min(i, j), max(i, j)), either orientation of the mask excluding the dyad, and a dyad has the same pbar and
+ * sd in both of its rows.  pbar and sd have the bits that dlsm_topk_accumulate returns for the dyad.  A row's list is
+ * kept sorted in the registers of one wavefront while its columns stream by: nothing of size T*N*N is stored or sorted.
+ *   row_blocks  NULL: every row; else n_row_blocks strictly ascending blocks of 32 rows (n_features > 4: 16 rows) in
+ *               0 .. ceil(N / rows of a block) - 1: only their rows are computed
+ *   partner     T*N*k int32: the partners of node i at t in rank order, then -1
+ *   value       T*N*k*2: (pbar, sd) of the same entries, then NaN
+ *   y           T*N*k int32: their bits of the network, then -1
+ *   eligible    T*N int32: the eligible partners of the row; -1 for the rows of blocks that are not listed (all padding)
+ * S < 2, among outside 0..4, largest not 0 or 1, k outside 1..64, among = 3 without a mask, row_blocks not ascending or
+ * out of range -> DLSM_E_ARG; a set diagonal or padding bit of `bits`, a radius <= 0 -> DLSM_E_DATA; samples that do
+ * not fit the device -> DLSM_E_LIMIT. */
+int dlsm_partners_accumulate(dlsm_chain *h, const uint32_t *bits, const uint32_t *mask, const double *Xs,
+                             const double *intercepts, const double *radii, int S, int among, int largest, int k,
+                             const int32_t *row_blocks, int n_row_blocks, int32_t *partner, double *value,
+                             int32_t *y, int32_t *eligible);
+
 /* ---- community structure of stored labellings ---------------------------- */
 /* The reference has modularity(Y, z) for one labelling on the host (network_statistics.py:31-61); the rest has no
  * counterpart.  zs S*T*N int64 labels in [0, K), 1 <= K <= 256 (packed to bytes on the device, staged in batches of
@@ -738,7 +762,8 @@ enum {
     DLSM_K_TOPK_COUNT = 12,        /* dlsm_topk_accumulate: k_topk_count and the histograms' hipMemsetAsync */
     DLSM_K_TOPK_SCAN = 13,         /* ... k_topk_threshold */
     DLSM_K_TOPK_EMIT = 14,         /* ... k_topk_emit */
-    DLSM_K_COUNT = 15
+    DLSM_K_PARTNERS = 15,          /* dlsm_partners_accumulate: k_partners_select */
+    DLSM_K_COUNT = 16
 };
 /* when enabled every launch of the kernel classes above is bracketed by HIP
  * events on the handle's stream; read returns accumulated ms and launches */
