@@ -6,6 +6,7 @@ first use and there is no CPU fallback (``dynetlsm_amd._lib.load`` raises when
 ``libdynetlsm_hip.so`` has not been built).
 """
 from .engine import Chain, SamplerGrid, EngineError  # noqa
+from .sparse import SparseNetwork  # noqa
 from . import network_likelihoods  # noqa
 from .lsm import DynamicNetworkLSM  # noqa
 from .hdp_lpcm import DynamicNetworkHDPLPCM  # noqa
@@ -29,7 +30,7 @@ from . import forecast  # noqa  (the one-step module; calling it is forecast_pat
 from .forecast_paths import ForecastResult  # noqa
 
 __version__ = '0.1.0'
-__all__ = ['Chain', 'SamplerGrid', 'EngineError', 'network_likelihoods',
+__all__ = ['Chain', 'SamplerGrid', 'EngineError', 'SparseNetwork', 'network_likelihoods',
            'DynamicNetworkLSM', 'DynamicNetworkHDPLPCM', 'DynamicNetworkLPCM',
            'DirectedCaseControlSampler', 'posterior_predictive_check', 'GofResult',
            'information_criteria', 'compare_information_criteria', 'ICResult', 'loo', 'compare_loo', 'LooResult',

@@ -11,6 +11,7 @@ from . import hdp_updates as hu
 from . import initialization as init_mod
 from .imputer import SimpleNetworkImputer
 from .metrics import FittedQuantities, missing_index
+from .sparse import SparseNetwork
 
 
 def check_random_state(seed):
@@ -82,7 +83,10 @@ class Estimator(FittedQuantities):
 # ---- before the loop ---------------------------------------------------------------------------
 def check_network(Y, copy=True):
     """``Y`` as a C-ordered float64 (T, N, N) array, copied as ``numpy.array(copy=copy)`` does;
-    ``copy=None`` keeps a float64 array as it is, whatever its order (for a caller that never reads it)"""
+    ``copy=None`` keeps a float64 array as it is, whatever its order (for a caller that never reads it).
+    A ``SparseNetwork`` passes through as it is (tested first: ``numpy.asarray`` of it would densify)."""
+    if isinstance(Y, SparseNetwork):
+        return Y
     Y = (np.asarray(Y, dtype=np.float64) if copy is None
          else np.array(Y, dtype=np.float64, copy=copy, order='C'))
     if Y.ndim != 3 or Y.shape[1] != Y.shape[2]:
@@ -99,6 +103,19 @@ def check_options(est):
     if est.n_control is not None and not est.is_directed:
         raise ValueError('The case-control likelihood currently only '
                          'supported for directed networks.')
+
+
+def sparse_network(est, Y):
+    """``Y`` if it is no ``SparseNetwork``; else the container as the estimator sees it - symmetrised
+    for an undirected model -, which has no missing dyads: neither ``impute`` nor ``prepare_missing``
+    is for it.  Returns ``(Y, is_sparse)``."""
+    if not isinstance(Y, SparseNetwork):
+        return Y, False
+    if est.sample_missing:
+        raise ValueError('sample_missing=True is not supported with a SparseNetwork: missing dyads '
+                         'have no sparse form yet (fit the dense array)')
+    est.nan_mask_ = None
+    return Y.as_seen(symmetric=not est.is_directed), True
 
 
 def impute(Y):
@@ -178,6 +195,8 @@ def open_chain(est, Y, X, intercept, radii, seed, network_from=None):
             n_control=est.n_control, n_resample=est.n_resample_control, chain=chain).init(Y)
     elif network_from is not None:
         network_from(chain)
+    elif isinstance(Y, SparseNetwork):
+        chain.upload_network_edges(Y)
     else:
         chain.upload_network(Y)
     chain.set_positions(X)
@@ -212,7 +231,7 @@ def warm_start(est, Y, rng, init, Y_raw=None, kmeans_on_device=False):
                                 sweep_algo=est.sweep_algo, **kw).fit(Y if Y_raw is None else Y_raw)
         X, intercept = emb.X_.copy(), np.array(emb.intercept_, dtype=np.float64)
         radii = emb.radii_.copy() if est.is_directed else None
-        if Y_raw is not None and np.any(Y_raw == -1):
+        if Y_raw is not None and not isinstance(Y_raw, SparseNetwork) and np.any(Y_raw == -1):
             Y = Y_raw.copy()
             Y[Y_raw == -1] = emb.probas_[Y_raw == -1] > 0.5
         emb.chain_.close()

@@ -83,6 +83,9 @@ SIGNATURES = {
     'dlsm_set_network_packed': (C.c_int, [handle_t, C.c_void_p, C.c_int64]),
     'dlsm_upload_edges': (C.c_int, [handle_t, c_i64_p, C.c_int, c_i64_p, C.c_int,
                                     c_i64_p]),
+    'dlsm_upload_network_edges': (C.c_int, [handle_t, c_i64_p, c_i32_p, c_i32_p]),
+    'dlsm_edge_table_widths': (C.c_int, [handle_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'dlsm_get_edges': (C.c_int, [handle_t, c_i64_p, c_i64_p, c_i64_p]),
     'dlsm_set_controls': (C.c_int, [handle_t, c_i64_p, c_i64_p, C.c_int]),
     'dlsm_get_controls': (C.c_int, [handle_t, c_i64_p, c_i64_p]),
     'dlsm_resample_controls': (C.c_int, [handle_t, C.c_uint32, C.c_int]),

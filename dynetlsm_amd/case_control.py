@@ -43,16 +43,33 @@ class DirectedCaseControlSampler(object):
         self.n_iter = 0
 
     def init(self, Y):
+        """``Y``: the dense (T, N, N) network, whose tables are built on the host and uploaded, or a
+        ``SparseNetwork``, whose tables the device builds from the lists (``degrees_``, ``in_edges_``
+        and ``out_edges_`` are then read back from the chain when they are first asked for)"""
+        from .sparse import SparseNetwork
         T, N, _ = Y.shape
         if isinstance(self.n_control, (numbers.Integral, np.integer)):
             self.n_control_ = int(self.n_control)
         else:
             self.n_control_ = int(self.n_control * N)
-        self.degrees_, self.in_edges_, self.out_edges_ = build_edge_lists(Y)
-        self.chain.upload_edges(self.in_edges_, self.out_edges_, self.degrees_)
+        for name in ('degrees_', 'in_edges_', 'out_edges_'):
+            self.__dict__.pop(name, None)
+        self._tables_on_chain = isinstance(Y, SparseNetwork)
+        if self._tables_on_chain:
+            self.chain.upload_network_edges(Y)
+        else:
+            self.degrees_, self.in_edges_, self.out_edges_ = build_edge_lists(Y)
+            self.chain.upload_edges(self.in_edges_, self.out_edges_, self.degrees_)
         self.sample(0)
         self.n_iter += 1
         return self
+
+    def __getattr__(self, name):
+        # (only reached when the attribute is not set: the tables of a device-built upload)
+        if name in ('degrees_', 'in_edges_', 'out_edges_') and self.__dict__.get('_tables_on_chain'):
+            self.in_edges_, self.out_edges_, self.degrees_ = self.chain.get_edge_tables()
+            return self.__dict__[name]
+        raise AttributeError(name)
 
     def sample(self, it):
         self.chain.resample_controls(it, self.n_control_)

@@ -250,6 +250,32 @@ class Chain(object):
         self._ck(self._L.dlsm_upload_edges(self._h, _p(ie), ie.shape[2], _p(oe),
                                            oe.shape[2], _p(dg)))
 
+    def upload_network_edges(self, net):
+        """the network from a ``SparseNetwork``'s lists: the packed rows of an undirected / directed chain,
+        the degree and edge tables of a case-control chain, built on the device"""
+        if tuple(net.shape) != (self.T, self.N, self.N):
+            raise ValueError('network has shape %s, expected %s' % (tuple(net.shape), (self.T, self.N, self.N)))
+        offsets, src, dst = net.by_time()
+        self._ck(self._L.dlsm_upload_network_edges(self._h, _p(offsets), _po(src), _po(dst)))
+
+    def edge_table_widths(self):
+        """(Din, Dout): the widths of a case-control chain's padded in / out edge tables"""
+        din, dout = C.c_int(0), C.c_int(0)
+        self._ck(self._L.dlsm_edge_table_widths(self._h, C.byref(din), C.byref(dout)))
+        return int(din.value), int(dout.value)
+
+    def get_edge_tables(self):
+        """(in_edges (T, N, Din), out_edges (T, N, Dout), degree (T, N, 2)) int64, as a case-control
+        chain holds them"""
+        din, dout = self.edge_table_widths()
+        ie = np.zeros((self.T, self.N, din), dtype=np.int64)
+        oe = np.zeros((self.T, self.N, dout), dtype=np.int64)
+        dg = np.zeros((self.T, self.N, 2), dtype=np.int64)
+        # (an empty table still needs an address: the engine copies nothing into it)
+        self._ck(self._L.dlsm_get_edges(self._h, _p(ie if ie.size else np.zeros(1, dtype=np.int64)),
+                                        _p(oe if oe.size else np.zeros(1, dtype=np.int64)), _p(dg)))
+        return ie, oe, dg
+
     def set_controls(self, control_nodes_in, control_nodes_out):
         ci = _i64(control_nodes_in); co = _i64(control_nodes_out)
         if ci.shape != co.shape or ci.shape[:2] != (self.T, self.N):

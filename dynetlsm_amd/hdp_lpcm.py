@@ -165,7 +165,8 @@ class DynamicNetworkHDPLPCM(Estimator):
         # missing dyads (hdp_lpcm.py:669-706): imputed once; undirected models also average
         # per-iteration Bernoulli draws of them after burn-in into ``missings_``, unless
         # sample_missing=True has the device draw them (Chain.impute_missing)
-        Y, miss, self._miss_index = _fit.prepare_missing(self, Y)
+        Y, sparse = _fit.sparse_network(self, Y)
+        Y, miss, self._miss_index = (Y, None, None) if sparse else _fit.prepare_missing(self, Y)
         T, N, _ = Y.shape
         K, D = self.n_components, check_n_features(self.n_features)
         rng = check_random_state(self.random_state)

@@ -53,8 +53,16 @@ def generalized_mds(chain, is_directed=False, lmbda=10, random_state=None,
 
 
 def initialize_radii(Y, reg=1e-5):
-    radii = 0.5 * (Y.sum(axis=(0, 1)) + Y.sum(axis=(0, 2)))
-    radii /= Y.sum()
+    """``Y``: the dense network or a ``SparseNetwork``, whose degree counts give the same sums - they
+    are whole numbers, so the radii are the dense path's to the bit"""
+    from .sparse import SparseNetwork
+    if isinstance(Y, SparseNetwork):
+        deg = Y.degrees().sum(axis=0)
+        radii = 0.5 * (deg[:, 0].astype(np.float64) + deg[:, 1].astype(np.float64))
+        radii /= np.float64(deg[:, 1].sum())
+    else:
+        radii = 0.5 * (Y.sum(axis=(0, 1)) + Y.sum(axis=(0, 2)))
+        radii /= Y.sum()
     if np.any(radii == 0.):
         radii += reg
         radii /= np.sum(radii)

@@ -28,6 +28,7 @@ from . import initialization as init_mod
 from ._fit import (Estimator, _ScalarMetropolis, _missing_attributes,
                    check_random_state)      # (other modules import check_random_state from here)
 from .metrics import missing_index
+from .sparse import SparseNetwork
 
 __all__ = ['DynamicNetworkLSM']
 
@@ -84,13 +85,15 @@ class DynamicNetworkLSM(Estimator):
     # -- fit ------------------------------------------------------------------
     def fit(self, Y, init=None):
         """Sample the posterior given the dynamic network ``Y`` (T, N, N),
-        float64 binary adjacency matrices.  ``init`` may give starting values
+        float64 binary adjacency matrices, or a ``SparseNetwork`` of its ties (no dense
+        tensor is formed; ``Y_fit_`` is then the container).  ``init`` may give starting values
         ``dict(X=..., intercept=..., radii=...)``; otherwise they come from the
         GMDS / conditional-MLE pipeline as in the reference (lsm.py:386-407)."""
         Y = _fit.check_network(Y, self.copy)
         _fit.check_options(self)
+        Y, sparse = _fit.sparse_network(self, Y)
         miss_index = None
-        if np.any(Y == -1):          # lsm.py:345-359
+        if not sparse and np.any(Y == -1):          # lsm.py:345-359
             if self.sample_missing:
                 miss_index = missing_index(Y, self.is_directed)
             Y = _fit.impute(Y)
@@ -136,7 +139,10 @@ class DynamicNetworkLSM(Estimator):
         T, N, _ = Y.shape
         with Chain(T, N, check_n_features(self.n_features),
                    'directed' if self.is_directed else 'undirected', device=self.device) as c0:
-            c0.upload_network(Y)
+            if isinstance(Y, SparseNetwork):
+                c0.upload_network_edges(Y)
+            else:
+                c0.upload_network(Y)
             X = init_mod.generalized_mds(c0, is_directed=self.is_directed, random_state=rng)
             if self.is_directed:
                 radii = init_mod.initialize_radii(Y)

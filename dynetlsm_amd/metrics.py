@@ -101,5 +101,6 @@ class FittedQuantities(object):
         """In-sample AUC of the selected model."""
         if not hasattr(self, 'X_'):
             raise ValueError('Model not fit.')
-        return network_auc(self.Y_fit_, self.probas_, is_directed=self.is_directed,
+        # (asarray: a sparse-fitted model's Y_fit_ is a SparseNetwork, densified here)
+        return network_auc(np.asarray(self.Y_fit_), self.probas_, is_directed=self.is_directed,
                            nan_mask=getattr(self, 'nan_mask_', None))

@@ -497,6 +497,10 @@ def fit_chains(estimator, Y, n_chains=None, init=None, backend=None, share_devic
       ``share_device0`` puts every rank on GPU 0 over gloo (a single-GPU box; tests).
 
     ``backend``: 'nccl' (= RCCL; the default on a GPU box) or 'gloo'."""
+    from .sparse import SparseNetwork
+    if isinstance(Y, SparseNetwork):
+        raise ValueError('fit_chains does not support a SparseNetwork yet: the ranks share the dense or the '
+                         'packed network (fit the chains one by one, or pass the dense array)')
     if 'RANK' in os.environ:
         if share_device0:
             os.environ['LOCAL_RANK'] = '0'

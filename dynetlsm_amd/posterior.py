@@ -12,6 +12,8 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from .sparse import SparseNetwork
+
 __all__ = ['cluster_counts', 'cluster_counts_t', 'renormalize_weights',
            'latent_marginal_loglikelihood', 'select_bic', 'posterior_cooccurrences',
            'expected_vi', 'minimize_posterior_expected_vi', 'procrustes_align_samples',
@@ -84,6 +86,14 @@ def _network_loglik(model, chain, sample_id):
     return chain.loglik_full([model.intercepts_[sample_id]])[0]
 
 
+def off_diagonal_sum(Y):
+    """the number of ties of the BIC's sample size (approx_bic.py:118-126); a ``SparseNetwork`` counts
+    its distinct pairs instead of densifying"""
+    if isinstance(Y, SparseNetwork):
+        return np.float64(Y.n_ties())
+    return np.sum(Y) - np.einsum('ikk', Y).sum()
+
+
 def select_bic(model, chain, n_burn):
     """approx_bic.py:79-162: per model size present in the kept samples, the MAP sample
     and its BIC; returns (bic[n_sizes, 4], models, counts)"""
@@ -99,7 +109,7 @@ def select_bic(model, chain, n_burn):
         radii = model.radiis_[map_id] if model.is_directed else None
         loglik_k = _network_loglik(model, chain, map_id)
         bic_k = -2 * loglik_k
-        off_diag_sum = np.sum(Y) - np.einsum('ikk', Y).sum()
+        off_diag_sum = off_diagonal_sum(Y)
         if model.is_directed:
             bic_k += (2 + N) * np.log(off_diag_sum)
         else:
@@ -202,8 +212,7 @@ def select_model_device(model, chain, n_burn):
     present = nk > 0
     counts = present.any(axis=1).sum(axis=1)                       # approx_bic.py:40-51
     model._counts_t = present.sum(axis=2).T                        # approx_bic.py:26-37: (T, S)
-    Y = model.Y_fit_
-    off_diag_sum = np.sum(Y) - np.einsum('ikk', Y).sum()
+    off_diag_sum = off_diagonal_sum(model.Y_fit_)
 
     def network_loglik(row):
         chain.set_positions(row['X'])

@@ -159,9 +159,9 @@ def synthetic_directed_from_model(T=5, N=10000, mean_degree=20.0, seed=0, interc
     5e8 Bernoulli draws take numpy a minute), so the network depends on where it was drawn; the
     parameters do not.
 
-    Returns dict(X, radii, intercepts, degree[T, N, 2], in_edges, out_edges, width) with the
+    Returns dict(X, radii, intercepts, degree[T, N, 2], in_edges, out_edges, width, network) with the
     tables in the layouts of case_control_likelihood.py:45-68 (zero padded, sources in increasing
-    order)."""
+    order) and ``network`` the ``SparseNetwork`` of the drawn edges, which ``fit`` takes."""
     rng = np.random.RandomState(seed)
     b_in, b_out = float(intercepts[0]), float(intercepts[1])
     radii = rng.dirichlet(np.ones(N) * 10)
@@ -242,5 +242,7 @@ def synthetic_directed_from_model(T=5, N=10000, mean_degree=20.0, seed=0, interc
         ds, ss = dst[t][order], src[t][order]
         start = np.concatenate([[0], np.cumsum(degree[t, :, 0])[:-1]])
         in_edges[t, ds, np.arange(ds.size) - start[ds]] = ss
+    from .sparse import SparseNetwork
+    network = SparseNetwork([np.stack([src[t], dst[t]], axis=1) for t in range(T)], N)
     return dict(X=X, radii=radii, intercepts=np.array([b_in, b_out]), degree=degree,
-                in_edges=in_edges, out_edges=out_edges, width=width)
+                in_edges=in_edges, out_edges=out_edges, width=width, network=network)

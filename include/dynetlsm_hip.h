@@ -78,6 +78,24 @@ int dlsm_set_network_packed(dlsm_chain *h, const uint32_t *buf, int64_t n_words)
  * in_edges T*N*Din, out_edges T*N*Dout, degree T*N*2 (col 0 in, col 1 out). */
 int dlsm_upload_edges(dlsm_chain *h, const int64_t *in_edges, int Din,
                       const int64_t *out_edges, int Dout, const int64_t *degree);
+/* The network as lists of ties: the pairs (src[e], dst[e]) of time step t are e in
+ * offsets[t] .. offsets[t+1] - 1 (offsets: T+1 values, offsets[0] = 0, non-decreasing; any order
+ * inside a step, duplicates allowed).  Replaces the float64 upload of lsm.py:341 and, on
+ * case-control chains, the host loops of case_control_likelihood.py:45-68; nothing of size N*N
+ * crosses the bus.  Leaves what the dense calls leave for the same network:
+ *   DLSM_UNDIRECTED             the packed words of dlsm_upload_network, both orientations of every pair
+ *   DLSM_DIRECTED               the packed words and their transpose
+ *   DLSM_DIRECTED_CASE_CONTROL  degree, in_edges, out_edges of dlsm_upload_edges (zero padded,
+ *                               neighbours ascending, widths = the largest in- / out-degree)
+ * A node index outside 0..N-1 or src == dst -> DLSM_E_DATA, bad offsets -> DLSM_E_ARG; after a
+ * failed call the chain has no network / edge lists. */
+int dlsm_upload_network_edges(dlsm_chain *h, const int64_t *offsets, const int32_t *src,
+                              const int32_t *dst);
+/* the case-control tables as the chain holds them: the widths, then in_edges T*N*Din,
+ * out_edges T*N*Dout, degree T*N*2 as int64 (in_edges_ / out_edges_ / degrees_ of
+ * case_control_likelihood.py:45-68) */
+int dlsm_edge_table_widths(dlsm_chain *h, int *Din, int *Dout);
+int dlsm_get_edges(dlsm_chain *h, int64_t *in_edges, int64_t *out_edges, int64_t *degree);
 /* control_nodes_in_/out_: T*N*C int64, -1 padded (case_control_likelihood.py:79-82) */
 int dlsm_set_controls(dlsm_chain *h, const int64_t *ctrl_in,
                       const int64_t *ctrl_out, int C);
