@@ -9,7 +9,7 @@ from scipy.special import gammaln, xlogy
 from .engine import Chain, SamplerGrid, check_n_features
 from . import hdp_updates as hu
 from . import initialization as init_mod
-from .imputer import SimpleNetworkImputer
+from .imputer import SimpleNetworkImputer, fill_missing_lists
 from .metrics import FittedQuantities, missing_index
 from .sparse import SparseNetwork
 
@@ -105,17 +105,43 @@ def check_options(est):
                          'supported for directed networks.')
 
 
-def sparse_network(est, Y):
+def sparse_network(est, Y, missing_lists=True):
     """``Y`` if it is no ``SparseNetwork``; else the container as the estimator sees it - symmetrised
-    for an undirected model -, which has no missing dyads: neither ``impute`` nor ``prepare_missing``
-    is for it.  Returns ``(Y, is_sparse)``."""
+    for an undirected model - and without missing dyads: neither ``impute`` nor ``prepare_missing`` is
+    for it.  Returns ``(Y, is_sparse, held)``.
+
+    A container that lists missing dyads is validated on a temporary chain of the estimator's model
+    (a dyad listed both as a tie and as missing is an error there), which also returns the canonical
+    index - the distinct dyads, row-major, i < j undirected.  They get their first fill
+    (``imputer.fill_missing_lists``) and the returned container is the filled one; ``held`` is
+    ``(Y with its lists, index)`` for ``Chain.set_missing_edges`` / ``_missing_attributes`` when
+    ``sample_missing`` is set, else None.  ``missing_lists=False``: the estimator takes no such
+    container.  The refusals answer before any chain is opened."""
     if not isinstance(Y, SparseNetwork):
-        return Y, False
-    if est.sample_missing:
-        raise ValueError('sample_missing=True is not supported with a SparseNetwork: missing dyads '
-                         'have no sparse form yet (fit the dense array)')
+        return Y, False, None
+    if Y.has_missing and not missing_lists:
+        raise ValueError('%s does not take a SparseNetwork that lists missing dyads: its warm start '
+                         're-imputes them from dense edge probabilities (fit the dense array)'
+                         % type(est).__name__)
+    if Y.has_missing and est.n_control is not None:
+        raise ValueError('n_control is not supported with a SparseNetwork that lists missing dyads: the '
+                         'case-control chain holds edge tables and control samples, not the dyads to fill')
+    if est.sample_missing and not Y.has_missing:
+        raise ValueError('sample_missing=True is not supported with a SparseNetwork that lists no '
+                         'missing dyads')
     est.nan_mask_ = None
-    return Y.as_seen(symmetric=not est.is_directed), True
+    symmetric = not est.is_directed
+    if not Y.has_missing:
+        return Y.as_seen(symmetric), True, None
+    T, N, _ = Y.shape
+    with Chain(T, N, check_n_features(est.n_features), model_name(est), device=est.device) as tmp:
+        tmp.upload_network_edges(Y)
+        tmp.set_missing_edges(Y, allow_ties=False)
+        index = tmp.get_missing_index()
+    n_observed = Y.degrees(symmetric)[:, :, 1].sum(axis=1)
+    ties = fill_missing_lists(index, n_observed, N) == 1
+    filled = Y.with_ties(index[ties]).without_missing().as_seen(symmetric)
+    return filled, True, ((Y, index) if est.sample_missing else None)
 
 
 def impute(Y):

@@ -196,6 +196,9 @@ SIGNATURES = {
                                       c_double_p, c_double_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint64,
                                       C.c_uint32, C.c_int, c_double_p, c_double_p, c_i32_p]),
     'dlsm_set_missing': (C.c_int, [handle_t, c_i32_p, C.c_int64]),
+    'dlsm_set_missing_edges': (C.c_int, [handle_t, c_i64_p, c_i32_p, c_i32_p, C.c_int]),
+    'dlsm_missing_count': (C.c_int, [handle_t, c_i64_p]),
+    'dlsm_get_missing_index': (C.c_int, [handle_t, c_i32_p]),
     'dlsm_impute_missing': (C.c_int, [handle_t, C.c_uint32, C.c_int]),
     'dlsm_missing_sampling': (C.c_int, [handle_t, C.c_int, C.c_int]),
     'dlsm_get_missing': (C.c_int, [handle_t, c_double_p, c_u32_p, c_i64_p]),

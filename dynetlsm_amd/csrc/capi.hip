@@ -2128,6 +2128,7 @@ int dlsm_timer_stop(dlsm_chain *h, double *ms) {
 }  // extern "C"
 
 #include "capi_edges.hpp"
+#include "capi_missing_edges.hpp"
 #include "capi_init.hpp"
 #include "capi_post.hpp"
 #include "capi_forecast.hpp"

@@ -302,6 +302,30 @@ class Chain(object):
         self._ck(self._L.dlsm_set_missing(self._h, _p(idx) if idx.shape[0] else None, idx.shape[0]))
         self.n_missing = int(idx.shape[0])
 
+    def set_missing_edges(self, net, allow_ties=False):
+        """the missing dyads from the missing lists of a ``SparseNetwork``: pairs in any order, duplicates
+        allowed, either orientation for the undirected model.  The tables are built on the device and are those
+        of ``set_missing`` for the distinct dyads in row-major order (``get_missing_index``).
+        ``allow_ties=False``: a listed dyad that is a tie of the uploaded network is an error."""
+        if tuple(net.shape) != (self.T, self.N, self.N):
+            raise ValueError('network has shape %s, expected %s' % (tuple(net.shape), (self.T, self.N, self.N)))
+        offsets, src, dst = net.missing_by_time()
+        self.n_missing = 0
+        self._ck(self._L.dlsm_set_missing_edges(self._h, _p(offsets), _po(src), _po(dst), int(bool(allow_ties))))
+        n = C.c_int64(0)
+        self._ck(self._L.dlsm_missing_count(self._h, C.byref(n)))
+        self.n_missing = int(n.value)
+
+    def get_missing_index(self):
+        """(n, 3) int64 rows (t, i, j) in the order of the accumulators: row-major after ``set_missing_edges``,
+        the caller's own list after ``set_missing``"""
+        n = C.c_int64(0)
+        self._ck(self._L.dlsm_missing_count(self._h, C.byref(n)))
+        tij = np.zeros((int(n.value), 3), dtype=np.int32)
+        if tij.shape[0]:
+            self._ck(self._L.dlsm_get_missing_index(self._h, _p(tij)))
+        return tij.astype(np.int64)
+
     def impute_missing(self, it, accumulate=False):
         """draw every missing dyad from its conditional at the current state (the draws of iteration
         ``it``) into the chain's network; asynchronous"""

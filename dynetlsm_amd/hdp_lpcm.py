@@ -165,8 +165,9 @@ class DynamicNetworkHDPLPCM(Estimator):
         # missing dyads (hdp_lpcm.py:669-706): imputed once; undirected models also average
         # per-iteration Bernoulli draws of them after burn-in into ``missings_``, unless
         # sample_missing=True has the device draw them (Chain.impute_missing)
-        Y, sparse = _fit.sparse_network(self, Y)
-        Y, miss, self._miss_index = (Y, None, None) if sparse else _fit.prepare_missing(self, Y)
+        Y, sparse, held = _fit.sparse_network(self, Y)
+        miss_lists, held_index = held if held is not None else (None, None)
+        Y, miss, self._miss_index = (Y, None, held_index) if sparse else _fit.prepare_missing(self, Y)
         T, N, _ = Y.shape
         K, D = self.n_components, check_n_features(self.n_features)
         rng = check_random_state(self.random_state)
@@ -210,7 +211,10 @@ class DynamicNetworkHDPLPCM(Estimator):
                            else 'host-driven')
         if self._miss_index is not None:
             self.loop_kind_ = 'host-driven'
-            chain.set_missing(self._miss_index)
+            if miss_lists is not None:      # (the same tables, from the container's lists)
+                chain.set_missing_edges(miss_lists, allow_ties=True)
+            else:
+                chain.set_missing(self._miss_index)
         # The device-resident loop keeps its trace in HBM; the three large arrays - Xs_
         # (320 KB per sample at T=10, N=2000), zs_, weights_ - reach the host only when somebody
         # reads them (__getattr__), and the post-loop processing runs where they lie.

@@ -112,7 +112,7 @@ class DynamicNetworkLPCM(Estimator):
         T, N, _ = Y_raw.shape
         K, D = self.n_components, check_n_features(self.n_features)
         rng = check_random_state(self.random_state)
-        Y_raw, sparse = _fit.sparse_network(self, Y_raw)
+        Y_raw, sparse, _ = _fit.sparse_network(self, Y_raw, missing_lists=False)
         Y, self._miss, self._miss_index = ((Y_raw, None, None) if sparse else
                                            _fit.prepare_missing(self, Y_raw))
         n_total = _fit.extend_n_iter(self)

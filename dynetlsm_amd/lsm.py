@@ -86,13 +86,14 @@ class DynamicNetworkLSM(Estimator):
     def fit(self, Y, init=None):
         """Sample the posterior given the dynamic network ``Y`` (T, N, N),
         float64 binary adjacency matrices, or a ``SparseNetwork`` of its ties (no dense
-        tensor is formed; ``Y_fit_`` is then the container).  ``init`` may give starting values
+        tensor is formed; ``Y_fit_`` is then the container - with the container's missing dyads, if
+        it lists any, filled once as ties or non-ties).  ``init`` may give starting values
         ``dict(X=..., intercept=..., radii=...)``; otherwise they come from the
         GMDS / conditional-MLE pipeline as in the reference (lsm.py:386-407)."""
         Y = _fit.check_network(Y, self.copy)
         _fit.check_options(self)
-        Y, sparse = _fit.sparse_network(self, Y)
-        miss_index = None
+        Y, sparse, held = _fit.sparse_network(self, Y)
+        miss_lists, miss_index = held if held is not None else (None, None)
         if not sparse and np.any(Y == -1):          # lsm.py:345-359
             if self.sample_missing:
                 miss_index = missing_index(Y, self.is_directed)
@@ -118,7 +119,10 @@ class DynamicNetworkLSM(Estimator):
         logp0 = self._log_prior(X, intercept, ip) + chain.loglik_full()
         self._impute = miss_index is not None and miss_index.shape[0] > 0
         if self._impute:             # lsm.py:525-545, with the draw written back
-            chain.set_missing(miss_index)
+            if miss_lists is not None:      # (the same tables, from the container's lists)
+                chain.set_missing_edges(miss_lists, allow_ties=True)
+            else:
+                chain.set_missing(miss_index)
             chain.missing_sampling(True, accumulate_after=self.n_burn_)
 
         t_loop = time.perf_counter()

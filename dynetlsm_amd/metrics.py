@@ -51,12 +51,18 @@ def missing_index(Y, is_directed):
 
 def heldout_scores(model, Y_true):
     """AUC and mean log-loss of ``model.missing_probas_`` (a ``sample_missing=True`` fit) against the
-    true values of the held-out dyads ``model.missing_index_`` in ``Y_true`` (T, N, N).  The AUC is
-    NaN when the held-out dyads are all of one class."""
+    true values of the held-out dyads ``model.missing_index_`` in ``Y_true`` (T, N, N), or in a
+    ``SparseNetwork`` of the whole network - looked up by sorted keys, in either orientation when the
+    model is undirected, with no dense tensor.  The AUC is NaN when the held-out dyads are all of one
+    class."""
+    from .sparse import SparseNetwork
     if not hasattr(model, 'missing_probas_'):
         raise ValueError('heldout_scores needs a fit with sample_missing=True on a network with -1 dyads')
     idx = model.missing_index_
-    y = np.asarray(Y_true)[idx[:, 0], idx[:, 1], idx[:, 2]]
+    if isinstance(Y_true, SparseNetwork):
+        y = Y_true.lookup(idx, symmetric=not model.is_directed)
+    else:
+        y = np.asarray(Y_true)[idx[:, 0], idx[:, 1], idx[:, 2]]
     if not np.isin(y, (0, 1)).all():
         raise ValueError('Y_true must hold 0 / 1 at the held-out dyads')
     p = np.clip(model.missing_probas_, 1e-15, 1 - 1e-15)

@@ -741,6 +741,23 @@ int dlsm_forecast_paths(dlsm_chain *h, const double *X0, const double *intercept
  * range, off its triangle or listed twice -> DLSM_E_DATA; a case-control chain (it holds edge lists)
  * -> DLSM_E_ARG; N >= 2^24 or n >= 2^30 -> DLSM_E_LIMIT.  Zeroes the accumulators. */
 int dlsm_set_missing(dlsm_chain *h, const int32_t *tij, int64_t n);
+/* the same list (lsm.py:345-359's nan mask, read by the step of lsm.py:525-545) as pairs: those of time step t
+ * are src / dst[offsets[t] .. offsets[t+1]), int32 node ids in any order, duplicates allowed.  The undirected
+ * model reads a pair in either orientation as the dyad {i, j}, the directed one as the arc i -> j.  Leaves
+ * exactly the tables dlsm_set_missing leaves for the distinct dyads in row-major (t, i, j) order, i < j
+ * undirected - the order of the accumulators and of dlsm_get_missing_index -, built on the device with nothing
+ * sorted.  allow_ties == 0: a listed dyad that is a tie of the uploaded network is an error (a held-out tie
+ * must have left the edge list); != 0: no such check (the network already holds imputed values).  A node id
+ * outside 0..N-1, src == dst or such a tie -> DLSM_E_DATA; a case-control chain, no network or bad offsets ->
+ * DLSM_E_ARG; N >= 2^24 or 2^30 dyads -> DLSM_E_LIMIT.  offsets all 0 clears the list and switches the
+ * sampling off; a failed call leaves the network and no list at all. */
+int dlsm_set_missing_edges(dlsm_chain *h, const int64_t *offsets, const int32_t *src, const int32_t *dst,
+                           int allow_ties);
+/* the number of dyads either call left (0: none set) */
+int dlsm_missing_count(dlsm_chain *h, int64_t *n);
+/* the list in the accumulators' order (lsm.py:345-359, :525-545: what the reference indexes its draws with):
+ * tij [n][3] rows (t, i, j), after dlsm_set_missing the caller's own rows.  Waits for the handle's stream. */
+int dlsm_get_missing_index(dlsm_chain *h, int32_t *tij);
 /* one step (lsm.py:525-545, hdp_lpcm.py:1039-1049) at the handle's current positions, intercepts and
  * radii with the draws of iteration `iter`; accumulate != 0 adds p and the drawn bit of every dyad to
  * the accumulators.  Enqueued on the handle's stream. */
