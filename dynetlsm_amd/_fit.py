@@ -334,7 +334,9 @@ def coefficient_steps(chain, rng, intercept, radii, ip, var, isamp, rsamp, group
         forth = _dirichlet_logpdf(x, rsamp.step_size * radii)
         ratio = ((ll_prop - ll_cur) + (back - forth) if group_proposal_terms
                  else ll_prop - ll_cur + back - forth)
-        accepted = int(not (np.log(rng.rand()) >= ratio))
+        # a NaN ratio (a proposal that is not finite: every gamma variate underflowed) rejects; the
+        # reference's `log(u) >= ratio` would accept it and keep NaN radii for good
+        accepted = int(np.log(rng.rand()) < ratio)
         ll = ll_cur
         if accepted:
             radii, ll = x, ll_prop

@@ -124,6 +124,7 @@ SIGNATURES = {
     'dlsm_trace_read': (C.c_int, [handle_t, C.c_int, C.c_int, c_double_p, c_double_p,
                                   c_double_p]),
     'dlsm_trace_read_radii': (C.c_int, [handle_t, C.c_int, C.c_int, c_double_p]),
+    'dlsm_lsm_get_radii_step': (C.c_int, [handle_t, c_double_p, c_double_p]),
     'dlsm_hdp_configure': (C.c_int, [handle_t, C.POINTER(HdpConfig), c_double_p, c_double_p]),
     'dlsm_hdp_get_config': (C.c_int, [handle_t, C.POINTER(HdpConfig)]),
     'dlsm_hdp_trace_alloc': (C.c_int, [handle_t, C.c_int, C.c_double]),

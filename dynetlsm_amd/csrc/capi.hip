@@ -939,6 +939,7 @@ int dlsm_loglik_full(dlsm_chain *h, int m, const double *intercepts, double *out
     NEED(h, m >= 1 && m <= 16, "m must be in 1..16");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = check_ready_loglik(h); if (rc) return rc;
+    h->radii_step_fresh = false;
     const int nic = h->model == DLSM_UNDIRECTED ? 1 : 2;
     if (!intercepts) NEED(h, m == 1, "intercepts == NULL requires m == 1");
     const Call call{h->stream, read_knobs()};
@@ -970,6 +971,7 @@ int dlsm_loglik_full_radii(dlsm_chain *h, const double *radii_alt, double *out) 
     NEED(h, h->model != DLSM_UNDIRECTED, "radii belong to directed models");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = check_ready_loglik(h); if (rc) return rc;
+    h->radii_step_fresh = false;
     rc = h2d(h, h->radii_alt, radii_alt, h->N); if (rc) return rc;
     // both candidates use the current intercepts
     HIPCHK(h, hipMemcpyAsync(h->dsmall, h->intercept, 2 * sizeof(double),
@@ -1013,6 +1015,7 @@ int dlsm_loglik_partial(dlsm_chain *h, int t, int j, const double *x, int with_p
     NEED(h, t >= 0 && t < h->T && j >= 0 && j < h->N, "node (t=%d, j=%d) out of range", t, j);
     HIPCHK(h, hipSetDevice(h->device));
     int rc = check_ready_partial(h, with_prior); if (rc) return rc;
+    h->radii_step_fresh = false;
     const double *d_x = nullptr;
     if (x) {
         memcpy(h->hsmall, x, sizeof(double) * h->D);
@@ -1702,6 +1705,7 @@ int dlsm_lsm_configure(dlsm_chain *h, const dlsm_lsm_config *cfg) {
     HIPCHK(h, hipMemcpy(h->lsm, &s, sizeof(s), hipMemcpyHostToDevice));
     h->lsm_cfg = *cfg;
     h->lsm_configured = true;
+    h->radii_step_fresh = false;
     return DLSM_OK;
 }
 
@@ -1973,13 +1977,32 @@ int dlsm_lsm_run(dlsm_chain *h, int first, int count, int procrustes_ref) {
         }
     }
     h->carry.reset();
+    h->radii_step_fresh = false;
     DISPATCH_D(h, h->D, {
         for (int it = first; it < first + count && !rc; ++it)
             rc = enqueue_lsm_iteration<DD>(h, call, it, false, it > h->lsm_cfg.n_iter_procrustes ? procrustes_ref : -1,
                                            false, call.knobs.tail_propose && it + 1 < first + count);
     });
     h->carry.reset();
+    h->radii_step_fresh = rc == DLSM_OK && h->model != DLSM_UNDIRECTED;
     return rc;
+}
+
+int dlsm_lsm_get_radii_step(dlsm_chain *h, double *proposal, double *terms) {
+    NEED(h, h && proposal && terms, "null argument");
+    NEED(h, h->model != DLSM_UNDIRECTED, "radii belong to directed models");
+    NEED(h, h->lsm_configured, "LSM chain not configured");
+    NEED(h, h->radii_step_fresh, "no radii step to read: call dlsm_lsm_run first (a log-likelihood call or "
+                                 "dlsm_lsm_configure since then has reused its buffers)");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    { int rc_ = check_pipe_err(h); if (rc_) return rc_; }
+    LsmDeviceState s;
+    HIPCHK(h, hipMemcpy(&s, h->lsm, sizeof(s), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(proposal, h->radii_alt, sizeof(double) * h->N, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(terms + 2, h->dsmall + 16, sizeof(double), hipMemcpyDeviceToHost));
+    terms[0] = s.dir_q; terms[1] = s.r_logu; terms[3] = s.ll_cur;
+    return DLSM_OK;
 }
 
 int dlsm_trace_read(dlsm_chain *h, int first, int count, double *Xs, double *intercepts,

@@ -236,6 +236,7 @@ int dlsm_hdp_configure(dlsm_chain *h, const dlsm_hdp_config *cfg, const double *
     s.mbar_total = s.mbar_positive = s.m00_total = s.m_rest_total = s.override_total = 0.0;
     HIPCHK(h, hipMemcpy(h->hdp, &s, sizeof(s), hipMemcpyHostToDevice));
     // the intercept's sampler shares the LSM loop's device state
+    h->radii_step_fresh = false;
     LsmDeviceState ls;
     memset(&ls, 0, sizeof(ls));
     ls.intercept_prior[0] = cfg->intercept_prior;
@@ -347,6 +348,7 @@ int dlsm_hdp_run(dlsm_chain *h, int first, int count) {
     int rc = check_ready_hdp(h); if (rc) return rc;
     const Call call{h->stream, read_knobs()};
     h->carry.reset();
+    h->radii_step_fresh = false;
     rc = hdp_fork_arm(h, call.knobs); if (rc) return rc;
     DISPATCH_D(h, h->D, {
         for (int it = first; it < first + count && !rc; ++it)

@@ -187,6 +187,9 @@ struct dlsm_chain {
     Dev<double> trace_X, trace_ic, trace_logp;
     Dev<double> trace_radii;
     int trace_n = 0;
+    // dlsm_lsm_run's last radii step is still where it left it (radii_alt, dsmall[16], the sampler's words):
+    // dlsm_lsm_get_radii_step; cleared by whatever writes one of them
+    bool radii_step_fresh = false;
     // one captured Gibbs iteration (hipGraph), replayed by dlsm_lsm_run
     hipGraph_t graph = nullptr; hipGraphExec_t graph_exec = nullptr;
     int graph_ref = -2, graph_algo = -1; bool graph_failed = false;

@@ -80,7 +80,9 @@ constexpr int DP_COLS = 7;         // A, B, C, E, sum x, sum r, zero flag
 //   dir_q = log Dir(radii | step x) - log Dir(x | step radii),
 // in three steps: gamma variates (one node per thread) + per-workgroup sums; normalise +
 // per-workgroup sums of the density terms; one workgroup puts them together (and repairs an
-// exact zero, metropolis.py:65-69, the slow way: it practically never happens).
+// exact zero, metropolis.py:65-69, the slow way).  A zero is a variate that underflowed:
+// U^(1 / a) at a concentration a = step * radii[i] below about 0.02, that is a radius that has
+// drifted below about 1e-7 at the default step - then at every iteration, otherwise never.
 __device__ __forceinline__ void dir_radii_gamma_wg(const ChainView &c, const LsmDeviceState *lsm,
                                                    const double *__restrict__ radii,
                                                    double *__restrict__ radii_alt,
@@ -303,7 +305,9 @@ __global__ __launch_bounds__(DR_THREADS) void k_dir_tail(
     const int it = (int)ir.get();
     // at the current ones: the value the intercept steps left
     const double ll_now = lsm->ll_cur;
-    const int accepted = !(lsm->r_logu >= (ll0 - ll_now) + lsm->dir_q);
+    // (a NaN ratio - every gamma variate underflowed, so the proposal is 0 / 0 - rejects: the
+    // reference's `log(u) >= ratio` would accept it and keep NaN radii for good)
+    const int accepted = lsm->r_logu < (ll0 - ll_now) + lsm->dir_q;
     double *row = trace_radii + (size_t)it * N;
     for (int i = tid; i < N; i += DR_THREADS) {
         const double r = accepted ? radii_alt[i] : radii[i];

@@ -464,7 +464,9 @@ __global__ __launch_bounds__(LL_THREADS) void k_loglik_directed(
                     L[m] -= log((1.0 + exp(Bs[m] + xa)) * (1.0 + exp(Bs[m] + xg)));
                 } else {
                     if (P[m] > 1e200) { L[m] -= log(P[m]); P[m] = 1.0; }
-                    P[m] *= fma(Es[m], fast_exp(xa), 1.0) * fma(Es[m], fast_exp(xg), 1.0);
+                    // (clamped: a radii proposal has entries down to 1e-114, and fast_exp's argument
+                    // reduction is lost beyond 1e45 - inf or NaN where the factor is 1; e^-800 is 0)
+                    P[m] *= fma(Es[m], fast_exp(fmax(xa, -800.0)), 1.0) * fma(Es[m], fast_exp(fmax(xg, -800.0)), 1.0);
                 }
             }
         }

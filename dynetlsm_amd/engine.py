@@ -684,6 +684,14 @@ class Chain(object):
         self._ck(self._L.dlsm_trace_read_radii(self._h, int(first), int(count), _p(out)))
         return out
 
+    def radii_step_read(self):
+        """the radii step of the last iteration ``lsm_run`` ran, accepted or not: (proposal (N,),
+        dict(dir_q, logu, ll_proposal, ll_current)); accepted iff logu < ll_proposal - ll_current + dir_q"""
+        x = np.zeros(self.N)
+        t = np.zeros(4)
+        self._ck(self._L.dlsm_lsm_get_radii_step(self._h, _p(x), _p(t)))
+        return x, dict(dir_q=t[0], logu=t[1], ll_proposal=t[2], ll_current=t[3])
+
     # -- starting values (SURVEY.md 8f-1) -----------------------------------
     def init_shortest_paths(self):
         self._ck(self._L.dlsm_init_shortest_paths(self._h))

@@ -225,6 +225,18 @@ int dlsm_trace_read(dlsm_chain *h, int first, int count, double *Xs,
                     double *intercepts, double *logps);
 /* rows first .. first+count-1 of the radii trace (count*N), directed models */
 int dlsm_trace_read_radii(dlsm_chain *h, int first, int count, double *radii);
+/* A read-only view of the radii step of the last iteration dlsm_lsm_run ran, accepted or not
+ * (directed and case-control handles): proposal[N] = the scaled-Dirichlet proposal, after the repair
+ * of an exact zero if there was one; terms[4] = the proposal density ratio
+ * log Dir(radii | step x) - log Dir(x | step radii), the log-uniform of the accept test, the network
+ * log-likelihood at the proposal, and the one at the radii the step started from (both at the
+ * intercepts the two intercept steps left).  The step was accepted if and only if
+ * terms[1] < (terms[2] - terms[3]) + terms[0]; a NaN on the right-hand side rejects.  Waits for the
+ * handle's stream and copies; no kernel runs.  An undirected or unconfigured handle, no
+ * dlsm_lsm_run (of at least one iteration) yet, or a dlsm_loglik_full, dlsm_loglik_full_radii,
+ * dlsm_loglik_partial, dlsm_lsm_configure, dlsm_hdp_configure or dlsm_hdp_run call since, which
+ * reuse the step's buffers -> DLSM_E_ARG. */
+int dlsm_lsm_get_radii_step(dlsm_chain *h, double *proposal, double *terms);
 
 /* ---- device-resident HDP-LPCM chain (hdp_lpcm.py:823-1069) --------------------------
  * the whole Gibbs iteration of DynamicNetworkHDPLPCM._fit on the device -

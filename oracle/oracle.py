@@ -579,7 +579,9 @@ class ScalarMetropolis(object):
                   dirichlet.logpdf(x, self.step_size * x0))
         u = rng.rand()
         accepted = 1
-        if np.log(u) >= ratio:
+        # (the reference tests `log(u) >= ratio`, which a NaN ratio - a proposal whose gamma variates all
+        # underflowed - passes as an acceptance; here, as on the device, it is a rejection: DESIGN.md)
+        if not (np.log(u) < ratio):
             x, accepted = x0, 0
         self.book(accepted)   # tune is None for the radii sampler (lsm.py:470)
         return x
@@ -708,10 +710,13 @@ def tune_step_size_dirichlet(step_size, acc_rate):
     return step_size
 
 
-def directed_coefficient_steps(state, it, loglik, isamp, rsamp, intercept_prior, intercept_var):
+def directed_coefficient_steps(state, it, loglik, isamp, rsamp, intercept_prior, intercept_var, details=None):
     """intercept_in, intercept_out (sample_coefficients.py:12-75) and radii (:91-121) steps of one
     directed iteration at ``state``'s positions, with the engine's Philox draws; updates the
-    state's intercepts and radii in place and returns the network log-likelihood of the new state"""
+    state's intercepts and radii in place and returns the network log-likelihood of the new state.
+    ``details`` (a dict) receives the radii step's intermediates: step, radii0 (where it started), gammas,
+    zero_repair, x (the proposal), q, logu, ll_cur, ll_prop, ratio, accepted.
+    A NaN acceptance ratio of the radii step rejects (the reference would accept it: DESIGN.md)."""
     from scipy.special import gammaln
     seed, chain = state.c.seed, state.c.chain
     X = state.X
@@ -735,8 +740,10 @@ def directed_coefficient_steps(state, it, loglik, isamp, rsamp, intercept_prior,
     N = radii.shape[0]
     step = rsamp.step_size
     g = np.array([philox_gamma(seed, chain, i, it, step * radii[i]) for i in range(N)])
-    x = g * (1.0 / g.sum())
-    if np.any(x == 0.):
+    with np.errstate(divide='ignore', invalid='ignore'):
+        x = g * (1.0 / g.sum())
+    repaired = bool(np.any(x == 0.))
+    if repaired:
         x = x + 1e-5
         x = x / np.sum(x)
     q = ((gammaln(step * x.sum()) - gammaln(step * x).sum() + ((step * x - 1) * np.log(radii)).sum()) -
@@ -744,7 +751,12 @@ def directed_coefficient_steps(state, it, loglik, isamp, rsamp, intercept_prior,
           ((step * radii - 1) * np.log(x)).sum()))
     ll_cur, ll_alt = loglik(X, b, radii), loglik(X, b, x)
     lu, _ = philox_uniform2(seed, 0xFFFFFFFF, 0, it, stream_word(chain, STREAM_RADII))
-    accepted = int(not (np.log(float(lu)) >= (ll_alt - ll_cur) + q))
+    logu = np.log(float(lu))
+    ratio = (ll_alt - ll_cur) + q
+    accepted = int(logu < ratio)
+    if details is not None:
+        details.update(step=step, radii0=radii.copy(), gammas=g, zero_repair=repaired, x=x.copy(), q=q,
+                       logu=logu, ll_cur=ll_cur, ll_prop=ll_alt, ratio=ratio, accepted=accepted)
     llf = ll_cur
     if accepted:
         radii[:] = x
@@ -754,7 +766,7 @@ def directed_coefficient_steps(state, it, loglik, isamp, rsamp, intercept_prior,
 
 
 def lsm_iteration_directed(state, it, loglik, isamp, rsamp, intercept_prior, intercept_var,
-                           X_ref=None):
+                           X_ref=None, details=None):
     """One iteration on ``state`` (ChainState, model 1 or 2; its X, intercept and radii are
     updated in place); ``loglik(X, intercept, radii)`` is the model's network log-likelihood;
     isamp[2], rsamp are ScalarMetropolis objects.  Returns the log-posterior trace value."""
@@ -764,6 +776,7 @@ def lsm_iteration_directed(state, it, loglik, isamp, rsamp, intercept_prior, int
     if X_ref is not None:
         X[:] = procrustes_rotation(X_ref, X)[0]
     X[:] = center(X)
-    llf = directed_coefficient_steps(state, it, loglik, isamp, rsamp, intercept_prior, intercept_var)
+    llf = directed_coefficient_steps(state, it, loglik, isamp, rsamp, intercept_prior, intercept_var,
+                                     details=details)
     return llf + lsm_log_prior(X, state.c.tau_sq, state.c.sigma_sq, state.intercept, intercept_prior,
                                intercept_var)

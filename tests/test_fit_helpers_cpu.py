@@ -164,6 +164,27 @@ def test_coefficient_steps_renormalises_a_zero_in_the_radii_proposal():
     assert np.array_equal(seen, want) and seen.min() > 0
 
 
+def test_coefficient_steps_rejects_a_radii_proposal_that_is_not_finite():
+    """every gamma variate of the Dirichlet draw underflowed: 0 / 0 in every coordinate.  The ratio is
+    NaN, and the step is a rejection - radii kept, nothing set on the chain, booked as rejected -
+    whichever way the ratio is summed"""
+    radii0 = np.array([0.1, 0.2, 0.3, 0.4])
+    for grouped in (False, True):
+        chain = FakeChain([0.7, -0.5], radii0.copy())
+        rng, rsamp = _ZeroDirichlet(0, np.full(4, np.nan)), Sampler(1e-3)
+        with np.errstate(invalid='ignore'):
+            ic, radii, ll = _fit.coefficient_steps(chain, rng, np.array([0.7, -0.5]), radii0.copy(), IP, VAR,
+                                                   [Sampler(0.8), Sampler(0.5)], rsamp,
+                                                   group_proposal_terms=grouped)
+        assert len(rng.alphas) == 1
+        seen = [c[1] for c in chain.calls if c[0] == 'loglik_full_radii'][0]
+        assert np.all(np.isnan(seen))                   # (no zero to repair: NaN == 0 is false)
+        assert rsamp.booked == [0]
+        assert 'set_radii' not in [c[0] for c in chain.calls]
+        assert np.array_equal(radii, radii0) and np.array_equal(chain.radii, radii0)
+        assert np.isfinite(ll) and ll == _ll(ic, radii0)
+
+
 # ---- run_ranges --------------------------------------------------------------------------------
 class CountingSampler:
     """the cadence of DirectedCaseControlSampler.resample, counting instead of drawing"""
